@@ -14,8 +14,14 @@ chunk loop would be split (guided_filter.rs:260-316), into contiguous chunk rows
     11-35), generated on its own device from the global synthetic definition;
   * weak scaling (`--scaling weak`): a (N*size, size, size) array, each rank owning a size^3 share.
 No data-path collective: the process group carries the barrier and the max over ranks of the timed
-region only. After timing, rank 0 checks a sample of its output chunks (corner, edge, interior)
-against the oracle (oracle/, the reference's per-chunk algorithm) and reports `parity`.
+region only.
+
+A plain run does only what the headline needs: set up, warm up, time `--steps` steps, write the
+outputs of the last timed step if `--dump-outputs DIR` is given, print the result line. `--full`
+adds everything else the line can carry, each after the timed region: rank 0's check of a sample
+of its output chunks (corner, edge, interior) against the oracle (oracle/, the reference's
+per-chunk algorithm) as `parity`, the CPU baseline, the other BASELINE configs (`extra_configs`)
+and, with N > 1 ranks, the distributed legs (`dist_configs`).
 """
 from __future__ import annotations
 
@@ -49,18 +55,28 @@ def parse():
     ap.add_argument("--size", type=int, default=N,
                     help="cube edge: the global volume (strong) or each rank's share (weak)")
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the oracle parity sample, the CPU "
+                         "baseline and the extra / distributed legs (each has its own switch "
+                         "below); without it only the headline is measured")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last step computed to "
+                         "DIR/<name>.npy (float32; outputs above 48 MiB as a fixed seeded sample "
+                         "of voxels plus the first and last plane)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-chunks", type=int, default=0, help="chunks in the CPU sample")
     ap.add_argument("--parity-chunks", type=int, default=6,
-                    help="output chunks checked against the oracle after timing (0: skip)")
+                    help="with --full: output chunks checked against the oracle after timing "
+                         "(0: skip)")
     ap.add_argument("--share", default=None, metavar="G/N",
                     help="1-GPU proxy of one rank of an N-GPU strong split: run only rank G's "
                          "chunk rows (+ 2r halo) of the volume on this GPU (no process group)")
     ap.add_argument("--radius", type=int, default=RADIUS,
                     help="guided-filter radius (default 4 = the metric; 2 = config G2 at --size 1024)")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the other BASELINE configs timed after the headline (G2, the "
-                         "config-T share, the config-P octant pyramid, the Gaussian)")
+                    help="with --full: skip the other BASELINE configs timed after the headline "
+                         "(G2, the config-T share, the config-P octant pyramid, the Gaussian)")
     ap.add_argument("--extra", default="g2,t_share,pyramid_octant,gaussian",
                     help="comma list of the extra legs to run")
     ap.add_argument("--dist-extra", default="t_series,p_pyramid",
@@ -189,6 +205,41 @@ def parity_sample(out_dev, a, gshape, radius: int, nchunks: int):
             "chunks": [list(c) for c in coords], "bit_exact_frac": round(exact / total, 4),
             "oracle": "oracle/zt_oracle.c per-chunk apply_ndarray on the 2r-halo block",
             "secs": round(time.perf_counter() - t0, 2)}
+
+
+DUMP_WHOLE_BYTES = 48 << 20  # an output up to this size is written whole
+DUMP_SAMPLE_VOXELS = 1 << 22  # else this many sampled voxels (16 MiB of f32) over all ranks ...
+DUMP_PLANE_BYTES = 16 << 20  # ... and, on one rank, the first and last plane if each fits this
+DUMP_SEED = 0x5EED2025
+
+
+def dump_outputs(dirpath: str, out, rank: int = 0, world: int = 1):
+    """--dump-outputs: write this rank's output of the last timed step (the tensor a caller of
+    zt_guided_filter_apply_slab receives) as float32 .npy files under `dirpath`, at most
+    DUMP_WHOLE_BYTES (48 MiB) of array data over all ranks. A small output is written
+    whole (`out`); a larger one as `out_sample`, its values at flat indices
+    numpy.random.default_rng(DUMP_SEED + rank).integers(0, out.numel(), DUMP_SAMPLE_VOXELS //
+    world) in that order, plus on a single rank `out_plane_first` / `out_plane_last` (axis 0).
+    The inputs are synthetic with a fixed seed, so the same arguments give the same files from
+    every build that computes the same thing. Returns the names written."""
+    import numpy as np
+    import torch
+    os.makedirs(dirpath, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    arrays = {}
+    n = out.numel()
+    if n * 4 * world <= DUMP_WHOLE_BYTES:
+        arrays["out" + sfx] = out
+    else:
+        k = max(1, DUMP_SAMPLE_VOXELS // world)
+        idx = np.random.default_rng(DUMP_SEED + rank).integers(0, n, size=k, dtype=np.int64)
+        arrays["out_sample" + sfx] = out.reshape(-1)[torch.from_numpy(idx).to(out.device)]
+        if world == 1 and out[0].numel() * 4 <= DUMP_PLANE_BYTES:
+            arrays["out_plane_first"], arrays["out_plane_last"] = out[0], out[-1]
+    for name, t in arrays.items():
+        np.save(os.path.join(dirpath, name + ".npy"),
+                np.ascontiguousarray(t.detach().cpu().numpy().astype(np.float32, copy=False)))
+    return sorted(arrays)
 
 
 def lib_hash() -> str:
@@ -711,6 +762,7 @@ def main():
                           device="cpu" if one_dev else dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         wall, kern_ms = float(tt[0]), float(tt[1])
+    dumped = dump_outputs(args.dump_outputs, out, rank, world) if args.dump_outputs else None
 
     voxels_rank = a.out_nz * size * size  # rank 0's share (the largest, or equal)
     voxels_all = gshape[0] * size * size if share is None else voxels_rank
@@ -764,15 +816,18 @@ def main():
                         "in_z": [a.in_z0, a.in_z0 + a.in_nz],
                         # what N such GPUs would aggregate if every share ran this fast
                         "projected_aggregate_gibs": round(value * share[1], 3)}
-    if rank == 0 and world == 1 and share is None and not args.no_cpu_baseline:
+    if dumped is not None:
+        res["dumped_outputs"] = dumped
+    full = args.full  # everything below is measured or checked only on request
+    if full and rank == 0 and world == 1 and share is None and not args.no_cpu_baseline:
         try:
             res["cpu_baseline"] = cpu_baseline(gshape, radius, args.cpu_chunks)
         except Exception as e:  # the baseline is reported, never required
             res["cpu_baseline"] = {"value": None, "error": str(e)}
-    if rank == 0 and args.parity_chunks > 0:
+    if full and rank == 0 and args.parity_chunks > 0:
         res["parity"] = parity_sample(out, a, gshape, radius, args.parity_chunks)
         res["parity_max_rel"] = res["parity"]["max_rel"]
-    if world == 1 and share is None and not args.no_extra and headline:
+    if full and world == 1 and share is None and not args.no_extra and headline:
         del slab, out
         torch.cuda.empty_cache()
         extra = {}
@@ -784,7 +839,7 @@ def main():
             except Exception as e:  # reported, never fatal to the headline line
                 extra[name] = {"error": f"{type(e).__name__}: {e}"}
         res["extra_configs"] = extra
-    if use_dist and world > 1 and share is None and not args.no_extra and headline:
+    if full and use_dist and world > 1 and share is None and not args.no_extra and headline:
         # configs[3] and [4] across the ranks (their own 8-way splits, round-robin over N ranks)
         del slab, out
         torch.cuda.empty_cache()

@@ -101,3 +101,34 @@ def test_sq_counters_follow_the_traffic_key(monkeypatch, tmp_path):
     assert bench.load_sq((2048,) * 3, 4, 1) is None  # traffic only, no SQ passes
     assert bench.load_sq((512,) * 3, 2, 1) is None  # another build
     assert bench.load_traffic((1024,) * 3, 2, 1) == 2.0e10
+
+
+def test_dump_outputs_whole_and_seeded_sample(monkeypatch, tmp_path):
+    """--dump-outputs: a small output is written whole; a larger one as a fixed seeded sample of
+    its voxels plus the first and last plane, the same files for the same output, float32, within
+    the size budget."""
+    import os
+    out = torch.arange(6 * 8 * 10, dtype=torch.float32).reshape(6, 8, 10)
+    assert bench.dump_outputs(str(tmp_path / "w"), out) == ["out"]
+    assert np.array_equal(np.load(tmp_path / "w" / "out.npy"), out.numpy())
+    monkeypatch.setattr(bench, "DUMP_WHOLE_BYTES", 1024)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_VOXELS", 64)
+    monkeypatch.setattr(bench, "DUMP_PLANE_BYTES", 8 * 10 * 4)
+    names = ["out_plane_first", "out_plane_last", "out_sample"]
+    for d in ("a", "b"):
+        assert bench.dump_outputs(str(tmp_path / d), out) == names
+    a = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in names}
+    b = {n: np.load(tmp_path / "b" / (n + ".npy")) for n in names}
+    assert all(a[n].dtype == np.float32 and np.array_equal(a[n], b[n]) for n in names)
+    idx = np.random.default_rng(bench.DUMP_SEED).integers(0, out.numel(), size=64, dtype=np.int64)
+    assert np.array_equal(a["out_sample"], out.numpy().reshape(-1)[idx])
+    assert np.array_equal(a["out_plane_first"], out[0].numpy())
+    assert np.array_equal(a["out_plane_last"], out[-1].numpy())
+    # N ranks share the budget: each writes its own seeded part of the sample and no planes
+    assert bench.dump_outputs(str(tmp_path / "r"), out, rank=1, world=2) == ["out_sample_rank1"]
+    assert np.load(tmp_path / "r" / "out_sample_rank1.npy").shape == (32,)
+    assert sorted(os.listdir(tmp_path / "r")) == ["out_sample_rank1.npy"]
+    # the real budget: whole output, or sample + two planes, stays under 64 MB
+    monkeypatch.undo()
+    assert bench.DUMP_WHOLE_BYTES <= 48 << 20
+    assert bench.DUMP_SAMPLE_VOXELS * 4 + 2 * bench.DUMP_PLANE_BYTES <= 48 << 20

@@ -9,6 +9,6 @@ mkdir -p "$OUT"
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -q -rf --timeout 120 --timeout-method thread \
   > "$OUT/pytest_gpu.log" 2>&1 || { echo "pytest failed rc=$?"; tail -20 "$OUT/pytest_gpu.log"; exit 1; }
 tail -2 "$OUT/pytest_gpu.log"
-timeout -k 10 300 python -u bench.py > "$OUT/bench.log" 2>&1 || { echo "bench failed rc=$?"; tail -20 "$OUT/bench.log"; exit 1; }
+timeout -k 10 300 python -u bench.py --full > "$OUT/bench.log" 2>&1 || { echo "bench failed rc=$?"; tail -20 "$OUT/bench.log"; exit 1; }
 tail -1 "$OUT/bench.log"
 bash tools/profile_round.sh "$OUT/prof"
