@@ -120,7 +120,7 @@ def test_pyramid_levels_bit_exact():
     ((37, 50, 71), "uint16"), ((64, 64, 64), "uint8"), ((9, 17, 33), "int16"),
     ((40, 36, 72), "float32"), ((24, 20, 16), "float64"), ((19, 32, 40), "int64"),
     ((16, 16, 264), "uint32"), ((70, 8, 8), "int8"), ((5, 300, 9), "uint16"),
-    # u8 / bool take pyramid3_u8_mean_kernel (16-byte rows, dot4 sums): aligned rows with partial
+    # u8 / bool take pyramid3_u8_kernel (16-byte rows, dot4 sums): aligned rows with partial
     # lanes, rows that are not whole 16-byte quads, odd extents
     ((33, 34, 35), "uint8"), ((12, 8, 160), "uint8"), ((18, 20, 40), "uint8"),
     ((16, 12, 1056), "uint8"), ((33, 34, 35), "bool"), ((12, 8, 160), "int8"),

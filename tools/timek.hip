@@ -65,7 +65,13 @@ int main(int argc, char** argv) {
     p.oz0 = p.oy0 = p.ox0 = 0; p.onz = p.ony = p.onx = n; p.zseg = (argc > 3 && atoi(argv[3]) > 0) ? atoi(argv[3]) : 256; p.eps = 2500.0f;
     hipStream_t s; CK(hipStreamCreate(&s));
     auto launch = [&](const GFParams& p0, hipStream_t st) -> hipError_t {
-        if (TK_LAUNCH == 0) return launch_fused_cfg<TK_R, TK_TY, TK_NT, TIN, float>(p0, st);
+        if (TK_LAUNCH == 0) {  // the product's plan (tile height fused_tile_y(TK_R)), zseg fixed
+            const FusedGeom g{p0.ny, p0.nx, p0.oy0, p0.ox0, p0.onz, p0.ony, p0.onx,
+                              p0.in_sz, p0.in_sy, p0.out_sz, p0.out_sy};
+            const FusedPlan pl = plan_fused(g, TK_R, (int)sizeof(TIN), 4, (uintptr_t)p0.in,
+                                            (uintptr_t)p0.out, 0, p0.zseg);
+            return launch_fused_cfg<TK_R, TK_NT, TIN, float>(p0, pl, st);
+        }
         using C = GFConfig<TK_R, TK_TY, TK_NT>;
         GFParams q = p0;
         volatile float one = 1.0f;

@@ -569,7 +569,7 @@ struct GFConfig {
 //   carry no per-lane count or zeroing logic and no branch.
 // MODE 1 (quad): every tile of a quad-aligned geometry (each 4-element quad of a global access
 //   wholly inside or wholly outside the domain / output box): unmasked accesses, the outside
-//   quads through kBadOff, per-lane clamped counts and zeroing (one grid: see launch_fused_cfg).
+//   quads through kBadOff, per-lane clamped counts and zeroing (one grid: see plan_fused, gf_plan.hpp).
 // MODE 2 (edge): the border tiles otherwise: element-wise masked accesses. Its grid covers all
 //   tiles; the interior ones (mode 0's) return at once. Separate kernels
 // rather than runtime branches keep each march free of control flow around its memory
@@ -1144,23 +1144,6 @@ __global__ __launch_bounds__(NT) void gf3d_fused_kernel(GFParams p) {
 // ---------------------------------------------------------------------------------------------
 // Launch: pick the tile configuration for the radius, dispatch dtypes.
 // ---------------------------------------------------------------------------------------------
-inline long long floor_div(long long a, long long b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
-inline long long ceil_div(long long a, long long b) { return -floor_div(-a, b); }
-
-// Interior tile range along one axis: tiles t with origin o0 + t*T such that the whole E2 apron
-// [o0 + t*T - 2R, o0 + t*T + T + 2R + slack) is inside [0, n) and the output tile inside
-// [o0, o_end). Returns [lo, hi) (empty when lo >= hi).
-inline void interior_tiles(long long o0, long long o_end, long long n, int T, int R, int slack,
-                           int ntiles, int& lo, int& hi) {
-    long long l = ceil_div(2LL * R - o0, T);
-    long long h = floor_div(std::min(n - 2LL * R - slack, o_end) - T - o0, T) + 1;
-    l = std::max(l, 0LL);
-    h = std::min(h, (long long)ntiles);
-    if (h < l) h = l;
-    lo = (int)l;
-    hi = (int)h;
-}
-
 // > 64 KB of dynamic LDS needs the per-function opt-in, once per (kernel, device): a bit per
 // device in a per-instantiation mask (one process may drive several devices).
 template <typename K>
@@ -1192,38 +1175,34 @@ inline hipError_t launch_fused_variant(const GFParams& p, long long nwg, hipStre
     return hipGetLastError();
 }
 
-template <int R, int TY, int NT, typename TIn, typename TOut>
-inline hipError_t launch_fused_cfg(const GFParams& p0, hipStream_t stream) {
+// Follows the plan (gf_plan.hpp: plan_fused makes every launch decision).
+template <int R, int NT, typename TIn, typename TOut>
+inline hipError_t launch_fused_cfg(const GFParams& p0, const FusedPlan& pl, hipStream_t stream) {
+    constexpr int TY = fused_tile_y(R);
     using C = GFConfig<R, TY, NT>;
+    static_assert(C::TX == kFusedTileX, "the plan's tile width is the kernel's");
     GFParams p = p0;
     {
         const float w3 = (float)(C::W3);
         volatile float one = 1.0f;  // IEEE division on the host: RN(1/W^3)
         p.rcp_w3 = one / w3;
     }
-    p.tiles_x = (p.onx + C::TX - 1) / C::TX;
-    p.tiles_y = (p.ony + TY - 1) / TY;
-    p.nseg = (p.onz + p.zseg - 1) / p.zseg;
-    // Interior tiles (mode 0): the whole E2 apron inside the domain, the tile inside the output
-    // box. Quad-aligned geometry (every quad starts at a multiple of 4 elements: the E2 apron at
-    // x0 - 2R, the output tile at x0; the domain / output box widths multiples of 4): no quad
-    // straddles a boundary, so the other tiles take the unmasked mode 1, else the masked mode 2.
-    const bool quad_ok = (p.ox0 % 4 == 0) && (R % 2 == 0) && (p.nx % 4 == 0) &&
-                         (p.onx % 4 == 0) && (p.in_sy % 4 == 0) && (p.in_sz % 4 == 0) &&
-                         (p.out_sy % 4 == 0) && (p.out_sz % 4 == 0) &&
-                         ((uintptr_t)p.in % (4 * sizeof(TIn)) == 0) &&
-                         ((uintptr_t)p.out % (4 * sizeof(TOut)) == 0);
+    p.zseg = pl.zseg;
+    p.tiles_x = pl.tiles_x;
+    p.tiles_y = pl.tiles_y;
+    p.nseg = pl.nseg;
+    p.itx0 = pl.itx0;
+    p.itx1 = pl.itx1;
+    p.ity0 = pl.ity0;
+    p.ity1 = pl.ity1;
     const long long n_all = (long long)p.tiles_x * p.tiles_y;
-    if (quad_ok) {
+    if (pl.mode1) {
         // one grid, every tile in mode 1. Measured at 2048^3 r=4: 30.2 ms, against 35.2 ms for
         // mode 0 + a second grid of the border tiles (that grid's tail) and 30.4 ms for one grid
         // choosing the class per workgroup (both marches in one kernel: more SGPR spills); mode 0
         // alone over every tile (border output wrong, a bound only) 29.1 ms.
-        p.itx0 = p.itx1 = p.ity0 = p.ity1 = 0;
         return launch_fused_variant<R, TY, NT, TIn, TOut, 1>(p, n_all * p.nseg, stream);
     }
-    interior_tiles(p.ox0, p.ox0 + p.onx, p.nx, C::TX, R, 0, p.tiles_x, p.itx0, p.itx1);
-    interior_tiles(p.oy0, p.oy0 + p.ony, p.ny, TY, R, 0, p.tiles_y, p.ity0, p.ity1);
     const long long n_int = (long long)(p.itx1 - p.itx0) * (p.ity1 - p.ity0);
     hipError_t e = hipSuccess;
     if (n_int > 0)
@@ -1233,22 +1212,18 @@ inline hipError_t launch_fused_cfg(const GFParams& p0, hipStream_t stream) {
     return e;
 }
 
-template <int R, int TY, int NT, typename TIn, typename TOut>
-inline hipError_t launch_fused_auto(const GFParams& p, hipStream_t stream) {
-    return launch_fused_cfg<R, TY, NT, TIn, TOut>(p, stream);
-}
-
 // Element-type pairs with a direct fused instantiation (the rest are staged through f32).
 inline bool fused_fast_dtype(int d) { return d == kF32 || d == kU16 || d == kU8 || d == kBool; }
 
-#define ZT_FUSED_PAIRS(R, TY, NT)                                                                 \
-    hipError_t launch_fused_radius_##R(const GFParams& p, int din, int dout, hipStream_t s) {     \
+#define ZT_FUSED_PAIRS(R, NT)                                                                     \
+    hipError_t launch_fused_radius_##R(const GFParams& p, const FusedPlan& pl, int din, int dout, \
+                                       hipStream_t s) {                                           \
         auto pick_out = [&](auto tin) -> hipError_t {                                             \
             using TI = decltype(tin);                                                             \
             switch (dout) {                                                                       \
-            case kF32: return launch_fused_auto<R, TY, NT, TI, float>(p, s);                      \
-            case kU16: return launch_fused_auto<R, TY, NT, TI, uint16_t>(p, s);                   \
-            case kU8: case kBool: return launch_fused_auto<R, TY, NT, TI, uint8_t>(p, s);         \
+            case kF32: return launch_fused_cfg<R, NT, TI, float>(p, pl, s);                       \
+            case kU16: return launch_fused_cfg<R, NT, TI, uint16_t>(p, pl, s);                    \
+            case kU8: case kBool: return launch_fused_cfg<R, NT, TI, uint8_t>(p, pl, s);          \
             default: return hipErrorInvalidValue;                                                 \
             }                                                                                     \
         };                                                                                        \

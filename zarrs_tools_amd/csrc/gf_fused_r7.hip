@@ -2,5 +2,5 @@
 #include "gf_fused.hpp"
 
 namespace zt {
-ZT_FUSED_PAIRS(7, 16, 1024)
+ZT_FUSED_PAIRS(7, 1024)
 }  // namespace zt

@@ -38,33 +38,32 @@ namespace zt {
 
 bool fused_supports_radius(int radius) { return radius >= 0 && radius <= kFusedMaxRadius; }
 
-int fused_tile_y(int radius) { return radius <= 4 ? 32 : 16; }  // must match gf_fused_r<R>.hip
 bool fused_direct_pair(int dtype_in, int dtype_out) {
     return fused_fast_dtype(dtype_in) && fused_fast_dtype(dtype_out);
 }
 
-hipError_t launch_fused_radius_0(const GFParams&, int, int, hipStream_t);
-hipError_t launch_fused_radius_1(const GFParams&, int, int, hipStream_t);
-hipError_t launch_fused_radius_2(const GFParams&, int, int, hipStream_t);
-hipError_t launch_fused_radius_3(const GFParams&, int, int, hipStream_t);
-hipError_t launch_fused_radius_4(const GFParams&, int, int, hipStream_t);
-hipError_t launch_fused_radius_5(const GFParams&, int, int, hipStream_t);
-hipError_t launch_fused_radius_6(const GFParams&, int, int, hipStream_t);
-hipError_t launch_fused_radius_7(const GFParams&, int, int, hipStream_t);
-hipError_t launch_fused_radius_8(const GFParams&, int, int, hipStream_t);
+hipError_t launch_fused_radius_0(const GFParams&, const FusedPlan&, int, int, hipStream_t);
+hipError_t launch_fused_radius_1(const GFParams&, const FusedPlan&, int, int, hipStream_t);
+hipError_t launch_fused_radius_2(const GFParams&, const FusedPlan&, int, int, hipStream_t);
+hipError_t launch_fused_radius_3(const GFParams&, const FusedPlan&, int, int, hipStream_t);
+hipError_t launch_fused_radius_4(const GFParams&, const FusedPlan&, int, int, hipStream_t);
+hipError_t launch_fused_radius_5(const GFParams&, const FusedPlan&, int, int, hipStream_t);
+hipError_t launch_fused_radius_6(const GFParams&, const FusedPlan&, int, int, hipStream_t);
+hipError_t launch_fused_radius_7(const GFParams&, const FusedPlan&, int, int, hipStream_t);
+hipError_t launch_fused_radius_8(const GFParams&, const FusedPlan&, int, int, hipStream_t);
 
-hipError_t launch_guided_fused(const GFParams& p, int dtype_in, int dtype_out, int radius,
-                               hipStream_t stream) {
+hipError_t launch_guided_fused(const GFParams& p, const FusedPlan& pl, int dtype_in,
+                               int dtype_out, int radius, hipStream_t stream) {
     switch (radius) {
-    case 0: return launch_fused_radius_0(p, dtype_in, dtype_out, stream);
-    case 1: return launch_fused_radius_1(p, dtype_in, dtype_out, stream);
-    case 2: return launch_fused_radius_2(p, dtype_in, dtype_out, stream);
-    case 3: return launch_fused_radius_3(p, dtype_in, dtype_out, stream);
-    case 4: return launch_fused_radius_4(p, dtype_in, dtype_out, stream);
-    case 5: return launch_fused_radius_5(p, dtype_in, dtype_out, stream);
-    case 6: return launch_fused_radius_6(p, dtype_in, dtype_out, stream);
-    case 7: return launch_fused_radius_7(p, dtype_in, dtype_out, stream);
-    case 8: return launch_fused_radius_8(p, dtype_in, dtype_out, stream);
+    case 0: return launch_fused_radius_0(p, pl, dtype_in, dtype_out, stream);
+    case 1: return launch_fused_radius_1(p, pl, dtype_in, dtype_out, stream);
+    case 2: return launch_fused_radius_2(p, pl, dtype_in, dtype_out, stream);
+    case 3: return launch_fused_radius_3(p, pl, dtype_in, dtype_out, stream);
+    case 4: return launch_fused_radius_4(p, pl, dtype_in, dtype_out, stream);
+    case 5: return launch_fused_radius_5(p, pl, dtype_in, dtype_out, stream);
+    case 6: return launch_fused_radius_6(p, pl, dtype_in, dtype_out, stream);
+    case 7: return launch_fused_radius_7(p, pl, dtype_in, dtype_out, stream);
+    case 8: return launch_fused_radius_8(p, pl, dtype_in, dtype_out, stream);
     default: return hipErrorInvalidValue;
     }
 }

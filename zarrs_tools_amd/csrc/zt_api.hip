@@ -128,39 +128,6 @@ void c_strides(const int64_t* shape, int ndim, int64_t* strides) {
     }
 }
 
-// Choose the z-march length for a fused launch: whole chunk depths when there is enough
-// parallelism, shorter segments for a single small block. Segments are a free choice (windows
-// are clamped at the array, not the segment), so large launches march two chunk depths while
-// they keep >= 4096 workgroups (16 per CU): each segment re-fills its z-windows over 2r + 1
-// warm-up slices and pads its steps to a multiple of 2r + 1 (2048^3 r=4: 31.4 -> 30.6 ms;
-// 384- and 1024-slice segments measured slower, tools/timek.sh; profiles/r02_ab_harness.txt).
-int choose_zseg(int onz, int tiles, int radius, int chunk_depth) {
-    const int target_wg = 1024;
-    int zseg = chunk_depth > 0 ? std::min(chunk_depth, onz) : onz;
-    if (zseg <= 0) zseg = 1;
-    if (chunk_depth > 0 && radius <= 2) {
-        // short windows (5-slice warm-up): up to 4 chunk depths while >= 512 workgroups (2 per CU)
-        // remain (1024^3 r=2: 3.46 -> 3.33 ms for one 1024-slice segment per tile)
-        for (int m = 4; m >= 2; m /= 2)
-            if ((int64_t)m * chunk_depth <= onz &&
-                (int64_t)tiles * ((onz + m * chunk_depth - 1) / (m * chunk_depth)) >= 512) {
-                zseg = m * chunk_depth;
-                break;
-            }
-    } else if (chunk_depth > 0 && 2LL * chunk_depth <= onz &&
-               (int64_t)tiles * ((onz + 2 * chunk_depth - 1) / (2 * chunk_depth)) >= 4096) {
-        zseg = 2 * chunk_depth;
-    }
-    int64_t wg = (int64_t)tiles * ((onz + zseg - 1) / zseg);
-    if (wg < target_wg && chunk_depth <= 0) {
-        int nseg = (target_wg + tiles - 1) / std::max(tiles, 1);
-        int minseg = std::max(8, 4 * radius);
-        zseg = std::max(minseg, (onz + nseg - 1) / nseg);
-        zseg = std::min(zseg, onz);
-    }
-    return zseg;
-}
-
 int radius_ok(int radius) {
     if (radius < 0 || radius > zt::kMaxRadius)
         return fail(ZT_ERR_INVALID_PARAMETERS,
@@ -253,12 +220,15 @@ int run_fused3(zt_ctx* ctx, int dtype_in, const void* in, const int64_t dom[3], 
         p.out_sz = oshape[1] * oshape[2];
         p.out_sy = oshape[2];
     }
-    const int ty = zt::fused_tile_y(radius);
-    int tiles = (int)(((p.onx + 63) / 64) * ((p.ony + ty - 1) / ty));
-    p.zseg = choose_zseg(p.onz, tiles, radius, chunk_depth);
+    // every launch decision (gf_plan.hpp), on the geometry and element types actually launched
+    const int dt_out = stage_out ? (int)zt::kF32 : dtype_out;
+    const zt::FusedGeom geom{p.ny, p.nx, p.oy0, p.ox0, p.onz, p.ony, p.onx,
+                             p.in_sz, p.in_sy, p.out_sz, p.out_sy};
+    const zt::FusedPlan plan =
+        zt::plan_fused(geom, radius, (int)zt::dtype_size(dtype_in), (int)zt::dtype_size(dt_out),
+                       (uintptr_t)p.in, (uintptr_t)p.out, chunk_depth);
     if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev0, ctx->cur));
-    hipError_t e = zt::launch_guided_fused(p, dtype_in, stage_out ? (int)zt::kF32 : dtype_out,
-                                           radius, ctx->cur);
+    hipError_t e = zt::launch_guided_fused(p, plan, dtype_in, dt_out, radius, ctx->cur);
     if (e != hipSuccess) return hip_fail(e, "guided filter fused kernel launch");
     if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev1, ctx->cur));
     if (stage_out) {

@@ -6,6 +6,8 @@
 
 #include <atomic>
 
+#include "gf_plan.hpp"
+
 namespace zt {
 
 constexpr int kMaxDims = 8;
@@ -47,7 +49,6 @@ struct NdGeom {
 };
 
 bool fused_supports_radius(int radius);
-int fused_tile_y(int radius);  // output tile height of the fused kernel for this radius
 // element-type pairs with a direct fused instantiation; others are staged through f32
 bool fused_direct_pair(int dtype_in, int dtype_out);
 hipError_t launch_reencode_cast(const void* in, int dtype_in, void* out, int dtype_out, int64_t n,
@@ -56,8 +57,9 @@ hipError_t launch_cast_to_f32_3d(const void* in, int dtype, int64_t sz, int64_t 
                                  int64_t nz, int64_t ny, int64_t nx, hipStream_t s);
 hipError_t launch_cast_from_f32_3d(const float* in, int dtype, void* out, int64_t sz, int64_t sy,
                                    int64_t nz, int64_t ny, int64_t nx, hipStream_t s);
-hipError_t launch_guided_fused(const GFParams& p, int dtype_in, int dtype_out, int radius,
-                               hipStream_t stream);
+// pl = plan_fused (gf_plan.hpp) of p's geometry; it overrides p's zseg / tile / interior fields
+hipError_t launch_guided_fused(const GFParams& p, const FusedPlan& pl, int dtype_in,
+                               int dtype_out, int radius, hipStream_t stream);
 // scratch must hold separable_scratch_floats(g.numel) floats: v | X (2n) | Y (2n), each region
 // starting on a 16-byte boundary (the f64 / float2 views of X and Y stay aligned for odd n)
 inline int64_t separable_pad(int64_t n) { return (n + 3) & ~(int64_t)3; }
