@@ -228,6 +228,32 @@ int zt_gaussian_apply_array(zt_ctx* ctx, int dtype_in, const void* in, int dtype
                             const int64_t* shape, int ndim, const int64_t* chunk_shape,
                             const float* sigma, const int64_t* kernel_half_size);
 
+/* ---- Gradient magnitude (src/filter/filters/gradient_magnitude.rs; src/filter/kernel.rs) ---- */
+
+/* GradientMagnitudeOperator (gradient_magnitude.rs:24-29). */
+enum { ZT_GM_SOBEL = 0, ZT_GM_CENTRAL_DIFFERENCE = 1 };
+/* GradientMagnitude::is_compatible (gradient_magnitude.rs:151-175): all 13 types in and out. */
+int zt_gradient_magnitude_is_compatible(int dtype_in, int dtype_out);
+/* GradientMagnitude::memory_per_chunk (gradient_magnitude.rs:177-195). */
+int zt_gradient_magnitude_memory_per_chunk(int dtype_in, int dtype_out,
+                                           const int64_t* chunk_shape, int ndim, uint64_t* bytes);
+/* GradientMagnitude::apply_ndarray + extract_subset + `as` casts of apply_chunk
+ * (gradient_magnitude.rs:91-96, :109-147; kernel.rs:75-129) on a C-order device block: per axis
+ * the triangle / difference passes in axis order (Sobel) or one difference pass
+ * (CentralDifference), g += s * s, sqrt; replicate edges at the block bounds. Writes the region
+ * [out_start, out_start + out_shape) to `out` (C order, out_shape). op: ZT_GM_*. Bit-identical to
+ * the reference. 3-D Sobel runs one fused z-march; other ranks and CentralDifference run pass
+ * by pass on device scratch. */
+int zt_gradient_magnitude_apply_ndarray(zt_ctx* ctx, int dtype_in, const void* in,
+                                        const int64_t* in_shape, int ndim,
+                                        const int64_t* out_start, const int64_t* out_shape,
+                                        int dtype_out, void* out, int op);
+/* GradientMagnitude::apply's chunk loop (gradient_magnitude.rs:197-274) over a device-resident
+ * C-order array: every chunk with its halo of 1, which equals one pass over the whole array. */
+int zt_gradient_magnitude_apply_array(zt_ctx* ctx, int dtype_in, const void* in, int dtype_out,
+                                      void* out, const int64_t* shape, int ndim,
+                                      const int64_t* chunk_shape, int op);
+
 /* ---- Zarr V3 store -> store path (host storage in and out) ----------------------------------
  * The reference's filters read and write Zarr arrays through zarrs (Array::retrieve_array_subset_
  * ndarray / store_array_subset_ndarray, guided_filter.rs:95-110; zarrs_ome.rs:226-232). These
@@ -345,6 +371,12 @@ int zt_store_gaussian(const char* in_path, const char* out_path, int dtype_out,
                       const char* encoding_json, const float* sigma,
                       const int64_t* kernel_half_size, int device, int64_t row_begin,
                       int64_t row_end, int nthreads, int flags, zt_store_stats* stats);
+/* zarrs_filter gradient-magnitude IN OUT [--operator OP] [--data-type T] over a store
+ * (GradientMagnitude::apply, gradient_magnitude.rs:197-274): as zt_store_guided_filter, halo 1;
+ * op: ZT_GM_*. */
+int zt_store_gradient_magnitude(const char* in_path, const char* out_path, int dtype_out,
+                                const char* encoding_json, int op, int device, int64_t row_begin,
+                                int64_t row_end, int nthreads, int flags, zt_store_stats* stats);
 /* One zarrs_ome level with --gaussian-sigma (apply_chunk_continuous_gaussian, zarrs_ome.rs:
  * 236-271): the Gaussian of each downsample input subset (plus its kernel_half_size halo), then
  * the mean downsample of that f32 block to the level's data type. */

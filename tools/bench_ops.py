@@ -4,6 +4,8 @@ pyramid (config P per GPU: a 2048^3 uint16 octant, factor 2, 5 levels) and the G
 (zarrs_filter gaussian 1.0,1.0,1.0 3,3,3 on 1024^3 f32, docs/zarrs_filter.md:107). One JSON line
 per operation with its HBM roofline fraction and a CPU baseline (the oracle's C restatement,
 one thread, on a bounded sample of the same workload).
+`--only gradient`: the gradient magnitude (Sobel) on 1024^3 f32, alternated with the Gaussian at
+kernel_half_size 1 on the same volume (its yardstick), windows of at least half a second.
 
 Algorithmic bytes: pyramid = level 0 read once + every level written once (2 B per u16
 element; the fused launches never read an intermediate level back); Gaussian = 4 B read + 4 B written per voxel (the separable passes' intermediates are
@@ -115,6 +117,69 @@ def bench_gaussian(n, reps):
             "cpu_baseline": {"gib_per_s": round(128 ** 3 * 4 / 2 ** 30 / cpu_s, 4), "cores": 1,
                              "kind": "port", "sample": "128^3 f32 block, oracle Gaussian (C "
                              "restatement of gaussian.rs:110-119 / kernel.rs:17-73)"}}
+
+
+def bench_gradient(n, rounds=5, window_s=0.5):
+    """zarrs_filter gradient-magnitude (Sobel) on n^3 f32 -> f32 through GradientMagnitude.apply,
+    alternated in one run with the Gaussian at sigma 1,1,1 / kernel_half_size 1,1,1 on the same
+    volume (the same 3x3x3 footprint and algorithmic bytes: the yardstick). Each window is device
+    events around enough calls for at least `window_s`, after a warm-up; `rounds` windows of each,
+    alternating. Algorithmic bytes: 4 B read + 4 B written per voxel."""
+    import math
+    import numpy as np
+    import torch
+    import zarrs_tools_amd as zt
+    from tests import gm_ref
+    ctx = zt.default_context(0)
+    x = zt.synth_step_noise_f32((n, n, n))
+    y = torch.empty_like(x)
+    chunk = (min(n, 256),) * 3
+    a_in, a_out = zt.DeviceArray(x, chunk), zt.DeviceArray(y, chunk)
+    gm = zt.GradientMagnitude("sobel")
+    gs = zt.Gaussian([1.0] * 3, [1] * 3)
+    stream = torch.cuda.current_stream()
+    ops = {"gradient": lambda: gm.apply(a_in, a_out, ctx=ctx),
+           "gaussian": lambda: gs.apply(a_in, a_out, ctx=ctx)}
+    # parity (bit-exact) of the corner region whose inputs lie in the block copied back
+    m = min(n - 1, 32)
+    ops["gradient"]()
+    torch.cuda.synchronize()
+    ref = gm_ref.apply_ndarray(x[:m + 1, :m + 1, :m + 1].cpu().numpy())[:m, :m, :m]
+    exact = bool(np.array_equal(y[:m, :m, :m].cpu().numpy(), ref))
+    reps = {}
+    for k, fn in ops.items():  # warm-up, then calls per window until a window lasts window_s
+        r = 8
+        while True:
+            t = timed(fn, stream, r)
+            if t * r >= window_s * 1e3:
+                break
+            r = math.ceil(window_s * 1e3 / t * 1.05) + 1
+        reps[k] = r
+    ms = {k: [] for k in ops}
+    for _ in range(rounds):
+        for k, fn in ops.items():
+            ms[k].append(timed(fn, stream, reps[k]))
+
+    def line(k):
+        v = sorted(ms[k])
+        med = v[len(v) // 2]
+        gbs = n ** 3 * 8 / (med / 1e3) / 1e9
+        return {"ms": round(med, 4), "ms_min": round(v[0], 4), "ms_max": round(v[-1], 4),
+                "spread": round((v[-1] - v[0]) / med, 4), "windows_ms": [round(t, 4) for t in ms[k]],
+                "calls_per_window": reps[k],
+                "gib_per_s": round(n ** 3 * 4 / 2 ** 30 / (med / 1e3), 3),
+                "roofline": {"bound": "hbm", "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS,
+                             "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4),
+                             "algorithmic_bytes": n ** 3 * 8}}
+
+    g, y_ = line("gradient"), line("gaussian")
+    return {"op": "gradient_magnitude sobel (device-resident)",
+            "config": {"shape": [n] * 3, "dtype": "float32", "chunk": list(chunk),
+                       "rounds": rounds, "window_s": window_s},
+            "parity_bit_exact": exact, **g,
+            "yardstick": {"op": "gaussian sigma 1,1,1 half 1,1,1 (device-resident), same volume, "
+                                "windows alternated with the gradient's", **y_},
+            "ratio_to_yardstick": round(g["ms"] / y_["ms"], 4)}
 
 
 def bench_guided4d(shape, chunk, radius, reps):
@@ -246,6 +311,8 @@ def main():
                   flush=True)
     if "gaussian" in only:
         print(json.dumps(bench_gaussian(a.gaussian_size, a.reps)), flush=True)
+    if "gradient" in only:  # with its Gaussian half-size-1 yardstick, alternated
+        print(json.dumps(bench_gradient(a.gaussian_size)), flush=True)
 
 
 if __name__ == "__main__":

@@ -16,6 +16,7 @@ from .filter import (  # noqa: E402
     DeviceArray,
     Downsample,
     Gaussian,
+    GradientMagnitude,
     GuidedFilter,
     default_context,
     dtype_of,
@@ -30,7 +31,7 @@ from .shard import OctantAssignment, SlabAssignment, octant_assignment, slab_ass
 
 __all__ = [
     "ArraySubset", "ArraySubsetOverlap", "Context", "DeviceArray", "Downsample", "DTYPES",
-    "FilterError", "Gaussian", "GuidedFilter", "InvalidParameters", "SlabAssignment", "UnsupportedDataType",
+    "FilterError", "Gaussian", "GradientMagnitude", "GuidedFilter", "InvalidParameters", "SlabAssignment", "UnsupportedDataType",
     "default_context", "dtype_of", "lib", "octant_assignment", "OctantAssignment", "pyramid",
     "pyramid_level_shapes", "slab_assignment",
     "synth_step_noise_f32", "synth_u16", "synth_box", "torch_dtype",

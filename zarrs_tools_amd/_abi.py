@@ -64,6 +64,9 @@ _STATUS_CLASS = {
 
 _lib = None
 
+# ZT_GM_* (GradientMagnitudeOperator, gradient_magnitude.rs:24-29)
+GM_OPERATORS = {"sobel": 0, "central_difference": 1}
+
 # flags of the store filters
 STORE_ERASE_OUTPUT_METADATA = 1
 STORE_FINISH_OUTPUT = 2
@@ -163,6 +166,13 @@ def lib() -> ctypes.CDLL:
                                        i64p], c_int),
         "zt_gaussian_apply_array": ([vp, c_int, vp, c_int, vp, i64p, c_int, i64p, fp, i64p],
                                     c_int),
+        "zt_gradient_magnitude_is_compatible": ([c_int, c_int], c_int),
+        "zt_gradient_magnitude_memory_per_chunk": ([c_int, c_int, i64p, c_int,
+                                                    ctypes.POINTER(ctypes.c_uint64)], c_int),
+        "zt_gradient_magnitude_apply_ndarray": ([vp, c_int, vp, i64p, c_int, i64p, i64p, c_int,
+                                                 vp, c_int], c_int),
+        "zt_gradient_magnitude_apply_array": ([vp, c_int, vp, c_int, vp, i64p, c_int, i64p,
+                                               c_int], c_int),
         "zt_synth_step_noise_f32": ([vp, vp, i64p, c_int, i64p, ctypes.c_int64, ctypes.c_uint64],
                                     c_int),
         "zt_synth_u16": ([vp, vp, i64p, c_int, i64p, ctypes.c_int64, ctypes.c_uint64], c_int),
@@ -195,6 +205,9 @@ def lib() -> ctypes.CDLL:
         "zt_store_gaussian": ([ctypes.c_char_p, ctypes.c_char_p, c_int, ctypes.c_char_p, fp, i64p,
                                c_int, ctypes.c_int64, ctypes.c_int64, c_int, c_int,
                                ctypes.POINTER(StoreStats)], c_int),
+        "zt_store_gradient_magnitude": ([ctypes.c_char_p, ctypes.c_char_p, c_int, ctypes.c_char_p,
+                                         c_int, c_int, ctypes.c_int64, ctypes.c_int64, c_int,
+                                         c_int, ctypes.POINTER(StoreStats)], c_int),
         "zt_store_downsample_gaussian": ([ctypes.c_char_p, ctypes.c_char_p, i64p, fp, i64p, c_int,
                                           ctypes.c_char_p, c_int, ctypes.c_int64, ctypes.c_int64,
                                           c_int, c_int, ctypes.POINTER(StoreStats)], c_int),

@@ -1248,6 +1248,56 @@ int zt_store_gaussian(const char* in_path, const char* out_path, int dtype_out,
     }
 }
 
+int zt_store_gradient_magnitude(const char* in_path, const char* out_path, int dtype_out,
+                                const char* encoding_json, int op, int device, int64_t row_begin,
+                                int64_t row_end, int nthreads, int flags, zt_store_stats* stats) {
+    try {
+        if (!in_path || !out_path)
+            return zt::set_last_error(ZT_ERR_INVALID_PARAMETERS, "null argument");
+        if (op != ZT_GM_SOBEL && op != ZT_GM_CENTRAL_DIFFERENCE)
+            return zt::set_last_error(ZT_ERR_INVALID_PARAMETERS,
+                                      "unknown gradient magnitude operator");
+        Array in = Array::open(in_path);
+        const int nd = in.ndim();
+        Array out = build_output(in, out_path, dtype_out, in.shape, encoding_json);
+        const int dt = out.dtype;
+        if (int rc = zt_gradient_magnitude_is_compatible(in.dtype, dt)) return rc;
+        if (flags & ZT_STORE_ERASE_OUTPUT_METADATA) out.erase_metadata();
+        const int64_t nz = in.shape[0];
+        RowOp rop;
+        rop.input_planes = [&](int64_t z0, int64_t z1, int64_t& a, int64_t& b) {
+            a = std::max<int64_t>(0, z0 - 1);  // ArraySubsetOverlap (gradient_magnitude.rs:82-86)
+            b = std::min(nz, z1 + 1);
+        };
+        const std::vector<int64_t> shape = in.shape;
+        const int din = in.dtype;
+        int64_t gplane = 1;
+        for (int d = 1; d < nd; ++d) gplane *= shape[d];
+        const bool fused = nd == 3 && op == ZT_GM_SOBEL;
+        rop.scratch_bytes = [&, fused](int64_t planes) -> uint64_t {
+            // fused 3-D Sobel: at most an f32 copy of the output rows (other output types);
+            // otherwise three f32 buffers of the slab
+            return (uint64_t)planes * gplane * (fused ? 4 : 12);
+        };
+        rop.apply = [&](zt_ctx* c, const void* slab, int64_t in0, int64_t in1, void* o,
+                        int64_t z0, int64_t z1) -> int {
+            // the slab is a block that carries the halo or reaches the array edge on axis 0 and
+            // spans the other axes: its result on [z0, z1) is the chunked result
+            std::vector<int64_t> bshape(shape), ostart(nd, 0), oshape(shape);
+            bshape[0] = in1 - in0;
+            ostart[0] = z0 - in0;
+            oshape[0] = z1 - z0;
+            return zt_gradient_magnitude_apply_ndarray(c, din, slab, bshape.data(), nd,
+                                                       ostart.data(), oshape.data(), dt, o, op);
+        };
+        run_pipeline(in, out, device, row_begin, row_end, nthreads, rop, stats);
+        if (flags & ZT_STORE_FINISH_OUTPUT) out.store_metadata();
+        return ZT_OK;
+    } catch (const std::exception& e) {
+        return report(e);
+    }
+}
+
 int zt_store_downsample_gaussian(const char* in_path, const char* out_path, const int64_t* stride,
                                  const float* sigma, const int64_t* kernel_half_size,
                                  int dtype_out, const char* encoding_json, int device,

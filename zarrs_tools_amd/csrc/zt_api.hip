@@ -923,6 +923,156 @@ int zt_gaussian_apply_array(zt_ctx* ctx, int dtype_in, const void* in, int dtype
                         kernel_half_size);
 }
 
+// ---- gradient magnitude (gradient_magnitude.rs) ---------------------------------------------------
+
+namespace {
+
+// GradientMagnitude::apply_ndarray on a C-order block, writing only the output region.
+int run_gradient_magnitude(zt_ctx* ctx, int dtype_in, const void* in, const int64_t* in_shape,
+                           int ndim, const int64_t* out_start, const int64_t* out_shape,
+                           int dtype_out, void* out, int op) {
+    const int64_t nout = numel(out_shape, ndim), nin = numel(in_shape, ndim);
+    if (nout == 0) return ZT_OK;
+    // 3-D Sobel: the fused z-march (f32 region; other output types through a cast)
+    if (ndim == 3 && op == ZT_GM_SOBEL) {
+        zt::GMSobel3 p{};
+        for (int d = 0; d < 3; ++d) {
+            p.n[d] = in_shape[d];
+            p.on[d] = out_shape[d];
+            p.o0[d] = out_start[d];
+        }
+        if (zt::gm_sobel3_supported(p)) {
+            const bool cast_out = dtype_out != zt::kF32;
+            if (cast_out)
+                if (int rc = ctx->ensure_scratch(sizeof(float) * (size_t)nout)) return rc;
+            float* dst = cast_out ? static_cast<float*>(ctx->scratch) : static_cast<float*>(out);
+            if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev0, ctx->cur));
+            hipError_t e = zt::launch_gm_sobel3(in, dtype_in, dst, p, ctx->cur);
+            if (e != hipSuccess) return hip_fail(e, "gradient magnitude z/y/x march launch");
+            if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev1, ctx->cur));
+            if (cast_out) {
+                e = zt::launch_cast_from_f32_3d(dst, dtype_out, out, 0, 0, 1, 1, nout, ctx->cur);
+                if (e != hipSuccess) return hip_fail(e, "gradient magnitude output cast");
+            }
+            return ZT_OK;
+        }
+    }
+    // the reference's passes on the whole block: staging_in / staging_out / gradient_magnitude
+    if (int rc = ctx->ensure_scratch(sizeof(float) * 3 * (size_t)nin)) return rc;
+    float* sa = static_cast<float*>(ctx->scratch);
+    float* sb = sa + nin;
+    float* g = sb + nin;
+    if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev0, ctx->cur));
+    for (int axis = 0; axis < ndim; ++axis) {
+        const float* s = nullptr;
+        if (op == ZT_GM_SOBEL) {
+            const void* src = in;
+            int sdt = dtype_in;
+            for (int i = 0; i < ndim; ++i) {
+                float* dst = (i & 1) ? sb : sa;
+                hipError_t e = zt::launch_gm_pass(src, sdt, dst, numel(in_shape, i), in_shape[i],
+                                                  numel(in_shape + i + 1, ndim - i - 1),
+                                                  i == axis, ctx->cur);
+                if (e != hipSuccess) return hip_fail(e, "gradient magnitude pass launch");
+                src = dst;
+                sdt = zt::kF32;
+            }
+            s = static_cast<const float*>(src);
+        } else {
+            hipError_t e = zt::launch_gm_pass(in, dtype_in, sa, numel(in_shape, axis),
+                                              in_shape[axis],
+                                              numel(in_shape + axis + 1, ndim - axis - 1), true,
+                                              ctx->cur);
+            if (e != hipSuccess) return hip_fail(e, "gradient magnitude pass launch");
+            s = sa;
+        }
+        hipError_t e = zt::launch_gm_accumulate(g, s, nin, axis == 0, ctx->cur);
+        if (e != hipSuccess) return hip_fail(e, "gradient magnitude accumulate launch");
+    }
+    zt::NdGeom geom{};
+    geom.ndim = ndim;
+    geom.numel = nin;
+    geom.out_numel = nout;
+    for (int d = 0; d < ndim; ++d) {
+        geom.shape[d] = in_shape[d];
+        geom.out_start[d] = out_start[d];
+        geom.out_shape[d] = out_shape[d];
+    }
+    hipError_t e = zt::launch_gm_finish(g, dtype_out, out, geom, ctx->cur);
+    if (e != hipSuccess) return hip_fail(e, "gradient magnitude finish launch");
+    if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev1, ctx->cur));
+    return ZT_OK;
+}
+
+int gm_op_ok(int op) {
+    if (op != ZT_GM_SOBEL && op != ZT_GM_CENTRAL_DIFFERENCE)
+        return fail(ZT_ERR_INVALID_PARAMETERS, "unknown gradient magnitude operator %d", op);
+    return ZT_OK;
+}
+
+}  // namespace
+
+int zt_gradient_magnitude_is_compatible(int dtype_in, int dtype_out) {
+    // gradient_magnitude.rs:151-175: every listed type is accepted for input and output.
+    return dtypes_ok(dtype_in, dtype_out);
+}
+
+int zt_gradient_magnitude_memory_per_chunk(int dtype_in, int dtype_out,
+                                           const int64_t* chunk_shape, int ndim,
+                                           uint64_t* bytes) {
+    if (int rc = dtypes_ok(dtype_in, dtype_out)) return rc;
+    if (int rc = check_shape(chunk_shape, ndim, "chunk_shape")) return rc;
+    if (!bytes) return fail(ZT_ERR_INVALID_PARAMETERS, "null pointer");
+    // gradient_magnitude.rs:177-195
+    uint64_t nin = 1;
+    for (int d = 0; d < ndim; ++d) nin *= (uint64_t)(chunk_shape[d] + 2);
+    const uint64_t nout = (uint64_t)numel(chunk_shape, ndim);
+    *bytes = nin * (zt::dtype_size(dtype_in) + 4 * 4) + nout * (4 + zt::dtype_size(dtype_out));
+    return ZT_OK;
+}
+
+int zt_gradient_magnitude_apply_ndarray(zt_ctx* ctx, int dtype_in, const void* in,
+                                        const int64_t* in_shape, int ndim,
+                                        const int64_t* out_start, const int64_t* out_shape,
+                                        int dtype_out, void* out, int op) {
+    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = dtypes_ok(dtype_in, dtype_out)) return rc;
+    if (int rc = check_shape(in_shape, ndim, "in_shape")) return rc;
+    if (int rc = gm_op_ok(op)) return rc;
+    if (!out_start || !out_shape) return fail(ZT_ERR_INVALID_PARAMETERS, "null output region");
+    for (int d = 0; d < ndim; ++d)
+        if (out_start[d] < 0 || out_shape[d] < 0 || out_start[d] + out_shape[d] > in_shape[d])
+            return fail(ZT_ERR_INVALID_PARAMETERS, "output region outside the block on axis %d",
+                        d);
+    if (numel(out_shape, ndim) == 0) return ZT_OK;
+    if (!in || !out) return fail(ZT_ERR_INVALID_PARAMETERS, "null data pointer");
+    DeviceGuard g(ctx->device);
+    return run_gradient_magnitude(ctx, dtype_in, in, in_shape, ndim, out_start, out_shape,
+                                  dtype_out, out, op);
+}
+
+int zt_gradient_magnitude_apply_array(zt_ctx* ctx, int dtype_in, const void* in, int dtype_out,
+                                      void* out, const int64_t* shape, int ndim,
+                                      const int64_t* chunk_shape, int op) {
+    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = dtypes_ok(dtype_in, dtype_out)) return rc;
+    if (int rc = check_shape(shape, ndim, "shape")) return rc;
+    if (int rc = gm_op_ok(op)) return rc;
+    if (!chunk_shape) return fail(ZT_ERR_INVALID_PARAMETERS, "null chunk_shape");
+    for (int d = 0; d < ndim; ++d)
+        if (chunk_shape[d] <= 0)
+            return fail(ZT_ERR_INVALID_PARAMETERS, "chunk extent must be positive");
+    if (numel(shape, ndim) == 0) return ZT_OK;
+    if (!in || !out) return fail(ZT_ERR_INVALID_PARAMETERS, "null data pointer");
+    // Every chunk with its halo of 1 (clamped to the array) equals the whole array with
+    // replicate edges at the array bounds: each pass reaches 1, so an index clamps inside a
+    // chunk's block only where it clamps at the array (as for the Gaussian above).
+    int64_t zero[ZT_MAX_DIMS] = {0};
+    DeviceGuard g(ctx->device);
+    return run_gradient_magnitude(ctx, dtype_in, in, shape, ndim, zero, shape, dtype_out, out,
+                                  op);
+}
+
 // ---- downsample ------------------------------------------------------------------------------
 
 int zt_downsample_is_compatible(int dtype_in, int dtype_out, int discrete) {

@@ -128,6 +128,28 @@ bool gaussian_zyx_supported(const GaussZYX& p, int dtype_in);
 hipError_t launch_gaussian_zyx(const void* in, int dtype_in, float* out, const GaussZYX& p,
                                hipStream_t s);
 
+// Gradient magnitude (gradient.hip; gradient_magnitude.rs:109-147, kernel.rs:75-129).
+// 3-D Sobel in one z-march: C-order input block n[3] of dtype_in, f32 output of the region
+// [o0, o0 + on) (C order, on[3]); edges clamp at the block bounds.
+constexpr int kGMSegMin = 32;  // fewest output slices per z segment
+struct GMSobel3 {
+    int64_t n[3], on[3], o0[3];
+};
+bool gm_sobel3_supported(const GMSobel3& p);
+// output slices per z segment of the launch (and the segment count)
+int gm_sobel3_zseg(const GMSobel3& p, int64_t* nseg);
+hipError_t launch_gm_sobel3(const void* in, int dtype_in, float* out, const GMSobel3& p,
+                            hipStream_t s);
+// The generic passes on a whole C-order block: one triangle (diff = false) or difference pass
+// along the axis of extent n (block = outer x n x inner, dtype_in -> f32); g = (first ? 0 : g) +
+// s * s; out = sqrt(g) on the region g.out_start / g.out_shape of the block g.shape, as dtype_out.
+hipError_t launch_gm_pass(const void* in, int dtype_in, float* out, int64_t outer, int64_t n,
+                          int64_t inner, bool diff, hipStream_t s);
+hipError_t launch_gm_accumulate(float* g, const float* sq, int64_t total, bool first,
+                                hipStream_t s);
+hipError_t launch_gm_finish(const float* g, int dtype_out, void* out, const NdGeom& geom,
+                            hipStream_t s);
+
 // Synthetic inputs
 hipError_t launch_synth_step_noise_f32(float* out, int64_t n, int64_t plane, int64_t nx_row,
                                        int64_t nx_global, int64_t z0, uint64_t seed,

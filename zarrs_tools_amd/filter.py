@@ -7,6 +7,9 @@ Names, argument meaning and error behaviour follow LDeakin/zarrs_tools 0.7.2:
   - ``Downsample`` <- src/filter/filters/downsample.rs (Downsample::new(stride, discrete,
     chunk_limit), input_subset :64, apply_ndarray_continuous :72, apply_ndarray_discrete :99,
     output_shape :162, apply :170)
+  - ``GradientMagnitude`` <- src/filter/filters/gradient_magnitude.rs (GradientMagnitude::new(
+    operator, chunk_limit), apply_chunk :68, apply_ndarray :109, is_compatible :151,
+    memory_per_chunk :177, apply :197)
   - ``ArraySubsetOverlap`` <- src/filter/array_subset_overlap.rs:4-52
 Arrays are device-resident torch tensors (torch is used only for device memory and streams);
 every computation runs in libzarrs_tools_amd.so through the C ABI.
@@ -347,6 +350,86 @@ class Gaussian:
             ctx.handle, DTYPES[input.dtype], _ptr(input.data.contiguous()), DTYPES[output.dtype],
             _ptr(output.data), i64_array(input.shape), nd, i64_array(output.chunk_shape), sig,
             half))
+
+
+def gm_operator(operator: str) -> int:
+    """GradientMagnitudeOperator (gradient_magnitude.rs:24-29) as the ABI's ZT_GM_* code."""
+    op = _abi.GM_OPERATORS.get(str(operator).replace("-", "_").lower())
+    if op is None:
+        raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS,
+                                     f"unknown gradient magnitude operator {operator!r} "
+                                     "(sobel or central_difference)")
+    return op
+
+
+class GradientMagnitude:
+    """gradient_magnitude.rs:55-275 — `GradientMagnitude::new(operator, chunk_limit)`: per axis
+    the triangle / difference passes (kernel.rs:75-129), sqrt of the summed squares."""
+
+    def __init__(self, operator: str = "sobel", chunk_limit: Optional[int] = None):
+        self._op = gm_operator(operator)
+        self.operator = {v: k for k, v in _abi.GM_OPERATORS.items()}[self._op]
+        self.chunk_limit = chunk_limit
+
+    def name(self) -> str:
+        return "gradient_magnitude"
+
+    def is_compatible(self, dtype_in: str, dtype_out: str) -> None:
+        for d in (dtype_in, dtype_out):
+            if d not in DTYPES:
+                raise _abi.UnsupportedDataType(_abi.ERR_UNSUPPORTED_DATA_TYPE,
+                                               f"Unsupported data type {d}")
+        check(lib().zt_gradient_magnitude_is_compatible(DTYPES[dtype_in], DTYPES[dtype_out]))
+
+    def memory_per_chunk(self, dtype_in: str, dtype_out: str, chunk_shape) -> int:
+        out = ctypes.c_uint64()
+        check(lib().zt_gradient_magnitude_memory_per_chunk(
+            DTYPES[dtype_in], DTYPES[dtype_out], i64_array(chunk_shape), len(chunk_shape),
+            ctypes.byref(out)))
+        return int(out.value)
+
+    def apply_ndarray(self, v, out_subset: Optional[ArraySubset] = None,
+                      dtype_out: Optional[str] = None, ctx: Optional[Context] = None):
+        """gradient_magnitude.rs:109-147 (+ extract_subset and the `as` casts of apply_chunk) on
+        a device block; returns `out_subset` of the result (whole block by default)."""
+        torch = _torch()
+        v = v.contiguous()
+        ctx = ctx or default_context(v.device.index)
+        dtype_in = dtype_of(v)
+        dtype_out = dtype_out or dtype_in
+        nd = v.dim()
+        if out_subset is None:
+            out_subset = ArraySubset((0,) * nd, tuple(v.shape))
+        out = torch.empty(out_subset.shape, dtype=torch_dtype(dtype_out), device=v.device)
+        check(lib().zt_gradient_magnitude_apply_ndarray(
+            ctx.handle, DTYPES[dtype_in], _ptr(v), i64_array(v.shape), nd,
+            i64_array(out_subset.start), i64_array(out_subset.shape), DTYPES[dtype_out],
+            _ptr(out), self._op))
+        return out
+
+    def apply_chunk(self, input: DeviceArray, output: DeviceArray, chunk_indices,
+                    ctx: Optional[Context] = None) -> None:
+        """gradient_magnitude.rs:68-107 on device-resident arrays."""
+        subset_output = output.chunk_subset_bounded(chunk_indices)
+        overlap = ArraySubsetOverlap(input.shape, subset_output, [1] * len(input.shape))
+        si = overlap.subset_input()
+        block = input.data[tuple(slice(s, s + n) for s, n in zip(si.start, si.shape))]
+        res = self.apply_ndarray(block, overlap.subset_dst_in_src(), output.dtype, ctx)
+        output.data[tuple(slice(s, s + n) for s, n in
+                          zip(subset_output.start, subset_output.shape))] = res
+
+    def apply(self, input: DeviceArray, output: DeviceArray,
+              ctx: Optional[Context] = None) -> None:
+        """gradient_magnitude.rs:197-274 over every output chunk (one pass over the array)."""
+        if tuple(output.shape) != tuple(input.shape):
+            raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS,
+                                         "input and output shapes differ")
+        ctx = ctx or default_context(input.data.device.index)
+        nd = len(input.shape)
+        check(lib().zt_gradient_magnitude_apply_array(
+            ctx.handle, DTYPES[input.dtype], _ptr(input.data.contiguous()), DTYPES[output.dtype],
+            _ptr(output.data), i64_array(input.shape), nd, i64_array(output.chunk_shape),
+            self._op))
 
 
 class Downsample:

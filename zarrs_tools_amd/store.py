@@ -323,6 +323,24 @@ def gaussian(input_path, output_path, sigma, kernel_half_size, data_type: Option
     return st.as_dict()
 
 
+def gradient_magnitude(input_path, output_path, operator: str = "sobel",
+                       data_type: Optional[str] = None, device: int = 0, rows=None,
+                       nthreads: int = 0, erase: bool = True, finish: bool = True, encoding=None,
+                       chunk_limit: int = 0) -> dict:
+    """zarrs_filter gradient-magnitude INPUT OUTPUT [--operator OP] [--data-type T]
+    (gradient_magnitude.rs:197-274); `operator`: "sobel" or "central_difference"."""
+    from .filter import gm_operator
+    op = gm_operator(operator)
+    set_chunk_limit(chunk_limit)
+    st = _abi.StoreStats()
+    r0, r1 = (0, -1) if rows is None else (int(rows[0]), int(rows[1]))
+    check(lib().zt_store_gradient_magnitude(_b(input_path), _b(output_path), _dt(data_type),
+                                            _enc(encoding), op, int(device), r0, r1,
+                                            int(nthreads), _flags(erase, finish),
+                                            ctypes.byref(st)))
+    return st.as_dict()
+
+
 def downsample_gaussian(input_path, output_path, stride, sigma, kernel_half_size,
                         data_type: Optional[str] = None, device: int = 0, rows=None,
                         nthreads: int = 0, erase: bool = True, finish: bool = True,
