@@ -254,6 +254,32 @@ int zt_gradient_magnitude_apply_array(zt_ctx* ctx, int dtype_in, const void* in,
                                       void* out, const int64_t* shape, int ndim,
                                       const int64_t* chunk_shape, int op);
 
+/* ---- Summed-area table (src/filter/filters/summed_area_table.rs) ---------------------------- */
+
+/* SummedAreaTable::is_compatible (summed_area_table.rs:110-134): all 13 types in and out. */
+int zt_summed_area_table_is_compatible(int dtype_in, int dtype_out);
+/* SummedAreaTable::memory_per_chunk (summed_area_table.rs:136-142): one input element plus one
+ * output element, as the reference has it (the chunk shape is validated only). */
+int zt_summed_area_table_memory_per_chunk(int dtype_in, int dtype_out, const int64_t* chunk_shape,
+                                          int ndim, uint64_t* bytes);
+/* SummedAreaTable::apply_dim for every axis, last to first (summed_area_table.rs:47-106, :172)
+ * on a C-order device block: `in as TOut` (:81), then per axis an inclusive running sum,
+ * `element += acc` left to right from a zero accumulator in TOut (:69, :94-97). Integer outputs
+ * wrap (the reference's release builds; its debug builds panic on overflow). Float outputs keep
+ * the reference's order, one rounding to TOut per add, so results are bit-identical. `carry`:
+ * NULL, or a device buffer of prod(shape[1:]) TOut elements that holds the seed plane of the
+ * axis-0 sum on entry (the reference's sum_last between chunks, :69, :94) and the last output
+ * plane on return; NULL seeds with zero. `in` and `out` must not overlap. */
+int zt_summed_area_table_apply_ndarray(zt_ctx* ctx, int dtype_in, const void* in,
+                                       const int64_t* shape, int ndim, int dtype_out, void* out,
+                                       void* carry);
+/* SummedAreaTable::apply's chunk loops (summed_area_table.rs:144-253) over a device-resident
+ * C-order array: the carried sums make them one pass per axis over the whole array.
+ * `chunk_shape` is validated only. */
+int zt_summed_area_table_apply_array(zt_ctx* ctx, int dtype_in, const void* in, int dtype_out,
+                                     void* out, const int64_t* shape, int ndim,
+                                     const int64_t* chunk_shape);
+
 /* ---- Zarr V3 store -> store path (host storage in and out) ----------------------------------
  * The reference's filters read and write Zarr arrays through zarrs (Array::retrieve_array_subset_
  * ndarray / store_array_subset_ndarray, guided_filter.rs:95-110; zarrs_ome.rs:226-232). These
@@ -377,6 +403,15 @@ int zt_store_gaussian(const char* in_path, const char* out_path, int dtype_out,
 int zt_store_gradient_magnitude(const char* in_path, const char* out_path, int dtype_out,
                                 const char* encoding_json, int op, int device, int64_t row_begin,
                                 int64_t row_end, int nthreads, int flags, zt_store_stats* stats);
+/* zarrs_filter summed-area-table IN OUT [--data-type T] over a store (SummedAreaTable::apply,
+ * summed_area_table.rs:144-253) in one read and one write of the store (the reference: one of
+ * each per axis): every chunk row along axis 0 is summed along its other axes on its own, and
+ * the axis-0 sum takes the previous row's last plane from a device buffer. The rows depend on
+ * each other in order, so there is no row range. Progress counts each output chunk once, not
+ * once per axis (:152-159). */
+int zt_store_summed_area_table(const char* in_path, const char* out_path, int dtype_out,
+                               const char* encoding_json, int device, int nthreads, int flags,
+                               zt_store_stats* stats);
 /* One zarrs_ome level with --gaussian-sigma (apply_chunk_continuous_gaussian, zarrs_ome.rs:
  * 236-271): the Gaussian of each downsample input subset (plus its kernel_half_size halo), then
  * the mean downsample of that f32 block to the level's data type. */

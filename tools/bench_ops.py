@@ -6,6 +6,9 @@ per operation with its HBM roofline fraction and a CPU baseline (the oracle's C 
 one thread, on a bounded sample of the same workload).
 `--only gradient`: the gradient magnitude (Sobel) on 1024^3 f32, alternated with the Gaussian at
 kernel_half_size 1 on the same volume (its yardstick), windows of at least half a second.
+`--only sat`: the summed-area table on 1024^3 float32 -> float32 and uint16 -> uint64, each
+alternated with the reencode cast of the same type pair on the same volume (one read and one
+write per voxel: the streaming yardstick).
 
 Algorithmic bytes: pyramid = level 0 read once + every level written once (2 B per u16
 element; the fused launches never read an intermediate level back); Gaussian = 4 B read + 4 B written per voxel (the separable passes' intermediates are
@@ -182,6 +185,86 @@ def bench_gradient(n, rounds=5, window_s=0.5):
             "ratio_to_yardstick": round(g["ms"] / y_["ms"], 4)}
 
 
+def bench_sat(n, din, dout, rounds=5, window_s=0.5):
+    """zarrs_filter summed-area-table on n^3 din -> dout through SummedAreaTable.apply (ndim
+    passes: the x scan reads din and writes dout, the others work on dout in place), alternated
+    in one run with zt_reencode_cast of the same type pair on the same volume (one streaming
+    pass, the yardstick). Windows as bench_gradient. Bytes per voxel: algorithmic = size(in) +
+    size(out); actual = that + 2 * (ndim - 1) * size(out) for the in-place passes. The time per
+    pass is the total over ndim; the split by kernel comes from a kernel trace of this run."""
+    import math
+    import numpy as np
+    import torch
+    import zarrs_tools_amd as zt
+    from zarrs_tools_amd import _abi
+    from zarrs_tools_amd.filter import DTYPES, _ptr
+    from tests import sat_ref
+    from tests.gpu_util import from_dev
+    ctx = zt.default_context(0)
+    if din == "float32":
+        x = zt.synth_step_noise_f32((n, n, n))
+    else:
+        x = zt.synth_u16((n, n, n))
+    y = torch.empty((n, n, n), dtype=zt.torch_dtype(dout), device=x.device)
+    chunk = (min(n, 256),) * 3
+    a_in, a_out = zt.DeviceArray(x, chunk, din), zt.DeviceArray(y, chunk, dout)
+    f = zt.SummedAreaTable()
+    stream = torch.cuda.current_stream()
+
+    def cast():
+        _abi.check(_abi.lib().zt_reencode_cast(ctx.handle, DTYPES[din], _ptr(x), DTYPES[dout],
+                                               _ptr(y), n ** 3))
+
+    ops = {"sat": lambda: f.apply(a_in, a_out, ctx=ctx), "cast": cast}
+    # parity (bit-exact): the corner block, whose sums need no element outside it
+    m = min(n, 48)
+    ops["sat"]()
+    torch.cuda.synchronize()
+    ref = sat_ref.sat(from_dev(x[:m, :m, :m], din), din, dout)
+    got = from_dev(y[:m, :m, :m], dout)
+    exact = bool(np.array_equal(got.view(np.uint8), ref.view(np.uint8)))
+    reps = {}
+    for k, fn in ops.items():  # warm-up, then calls per window until a window lasts window_s
+        r = 8
+        while True:
+            t = timed(fn, stream, r)
+            if t * r >= window_s * 1e3:
+                break
+            r = math.ceil(window_s * 1e3 / t * 1.05) + 1
+        reps[k] = r
+    ms = {k: [] for k in ops}
+    for _ in range(rounds):
+        for k, fn in ops.items():
+            ms[k].append(timed(fn, stream, reps[k]))
+    si, so, nd = x.element_size(), y.element_size(), 3
+    alg = n ** 3 * (si + so)
+    act = alg + n ** 3 * 2 * (nd - 1) * so
+
+    def line(k, nbytes_alg, nbytes_act):
+        v = sorted(ms[k])
+        med = v[len(v) // 2]
+        g_alg, g_act = nbytes_alg / (med / 1e3) / 1e9, nbytes_act / (med / 1e3) / 1e9
+        return {"ms": round(med, 4), "ms_min": round(v[0], 4), "ms_max": round(v[-1], 4),
+                "spread": round((v[-1] - v[0]) / med, 4), "windows_ms": [round(t, 4) for t in ms[k]],
+                "calls_per_window": reps[k],
+                "roofline": {"bound": "hbm", "achieved": round(g_alg, 1), "peak": HBM_PEAK_GBS,
+                             "unit": "GB/s", "frac": round(g_alg / HBM_PEAK_GBS, 4),
+                             "algorithmic_bytes": nbytes_alg},
+                "roofline_pass_bytes": {"achieved": round(g_act, 1),
+                                        "frac": round(g_act / HBM_PEAK_GBS, 4),
+                                        "bytes": nbytes_act}}
+
+    s, y_ = line("sat", alg, act), line("cast", alg, alg)
+    return {"op": f"summed_area_table {din} -> {dout} (device-resident)",
+            "config": {"shape": [n] * 3, "dtype_in": din, "dtype_out": dout, "chunk": list(chunk),
+                       "rounds": rounds, "window_s": window_s, "passes": nd},
+            "parity_bit_exact": exact, **s, "ms_per_pass": round(s["ms"] / nd, 4),
+            "yardstick": {"op": f"reencode cast {din} -> {dout} (device-resident), same volume, "
+                                "windows alternated with the table's", **y_},
+            "ratio_to_yardstick": round(s["ms"] / y_["ms"], 4),
+            "ratio_to_yardstick_per_pass_byte": round((s["ms"] / act) / (y_["ms"] / alg), 4)}
+
+
 def bench_guided4d(shape, chunk, radius, reps):
     """Config T per GPU: a (T, Z, Y, X) f32 time-series share, chunks
     (4, 256, 256, 256), eps 2500. 4-D arrays take the separable per-axis path."""
@@ -313,6 +396,9 @@ def main():
         print(json.dumps(bench_gaussian(a.gaussian_size, a.reps)), flush=True)
     if "gradient" in only:  # with its Gaussian half-size-1 yardstick, alternated
         print(json.dumps(bench_gradient(a.gaussian_size)), flush=True)
+    if "sat" in only:  # each with its reencode-cast yardstick, alternated
+        for din, dout in (("float32", "float32"), ("uint16", "uint64")):
+            print(json.dumps(bench_sat(a.gaussian_size, din, dout)), flush=True)
 
 
 if __name__ == "__main__":

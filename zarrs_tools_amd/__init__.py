@@ -18,6 +18,7 @@ from .filter import (  # noqa: E402
     Gaussian,
     GradientMagnitude,
     GuidedFilter,
+    SummedAreaTable,
     default_context,
     dtype_of,
     pyramid,
@@ -31,7 +32,8 @@ from .shard import OctantAssignment, SlabAssignment, octant_assignment, slab_ass
 
 __all__ = [
     "ArraySubset", "ArraySubsetOverlap", "Context", "DeviceArray", "Downsample", "DTYPES",
-    "FilterError", "Gaussian", "GradientMagnitude", "GuidedFilter", "InvalidParameters", "SlabAssignment", "UnsupportedDataType",
+    "FilterError", "Gaussian", "GradientMagnitude", "GuidedFilter", "InvalidParameters", "SlabAssignment", "SummedAreaTable",
+    "UnsupportedDataType",
     "default_context", "dtype_of", "lib", "octant_assignment", "OctantAssignment", "pyramid",
     "pyramid_level_shapes", "slab_assignment",
     "synth_step_noise_f32", "synth_u16", "synth_box", "torch_dtype",

@@ -173,6 +173,13 @@ def lib() -> ctypes.CDLL:
                                                  vp, c_int], c_int),
         "zt_gradient_magnitude_apply_array": ([vp, c_int, vp, c_int, vp, i64p, c_int, i64p,
                                                c_int], c_int),
+        "zt_summed_area_table_is_compatible": ([c_int, c_int], c_int),
+        "zt_summed_area_table_memory_per_chunk": ([c_int, c_int, i64p, c_int,
+                                                   ctypes.POINTER(ctypes.c_uint64)], c_int),
+        "zt_summed_area_table_apply_ndarray": ([vp, c_int, vp, i64p, c_int, c_int, vp, vp],
+                                               c_int),
+        "zt_summed_area_table_apply_array": ([vp, c_int, vp, c_int, vp, i64p, c_int, i64p],
+                                             c_int),
         "zt_synth_step_noise_f32": ([vp, vp, i64p, c_int, i64p, ctypes.c_int64, ctypes.c_uint64],
                                     c_int),
         "zt_synth_u16": ([vp, vp, i64p, c_int, i64p, ctypes.c_int64, ctypes.c_uint64], c_int),
@@ -208,6 +215,8 @@ def lib() -> ctypes.CDLL:
         "zt_store_gradient_magnitude": ([ctypes.c_char_p, ctypes.c_char_p, c_int, ctypes.c_char_p,
                                          c_int, c_int, ctypes.c_int64, ctypes.c_int64, c_int,
                                          c_int, ctypes.POINTER(StoreStats)], c_int),
+        "zt_store_summed_area_table": ([ctypes.c_char_p, ctypes.c_char_p, c_int, ctypes.c_char_p,
+                                        c_int, c_int, c_int, ctypes.POINTER(StoreStats)], c_int),
         "zt_store_downsample_gaussian": ([ctypes.c_char_p, ctypes.c_char_p, i64p, fp, i64p, c_int,
                                           ctypes.c_char_p, c_int, ctypes.c_int64, ctypes.c_int64,
                                           c_int, c_int, ctypes.POINTER(StoreStats)], c_int),

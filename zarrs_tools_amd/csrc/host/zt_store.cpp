@@ -1298,6 +1298,57 @@ int zt_store_gradient_magnitude(const char* in_path, const char* out_path, int d
     }
 }
 
+int zt_store_summed_area_table(const char* in_path, const char* out_path, int dtype_out,
+                               const char* encoding_json, int device, int nthreads, int flags,
+                               zt_store_stats* stats) {
+    try {
+        if (!in_path || !out_path)
+            return zt::set_last_error(ZT_ERR_INVALID_PARAMETERS, "null argument");
+        Array in = Array::open(in_path);
+        const int nd = in.ndim();
+        Array out = build_output(in, out_path, dtype_out, in.shape, encoding_json);
+        const int dt = out.dtype;
+        if (int rc = zt_summed_area_table_is_compatible(in.dtype, dt)) return rc;
+        if (flags & ZT_STORE_ERASE_OUTPUT_METADATA) out.erase_metadata();
+        RowOp rop;
+        rop.input_planes = [&](int64_t z0, int64_t z1, int64_t& a, int64_t& b) {
+            a = z0;  // no halo: a chunk row spans the other axes, whose sums are self-contained
+            b = z1;
+        };
+        const std::vector<int64_t> shape = in.shape;
+        const int din = in.dtype;
+        uint64_t carry_bytes = out.esz;
+        for (int d = 1; d < nd; ++d) carry_bytes *= (uint64_t)shape[d];
+        rop.scratch_bytes = [&](int64_t) -> uint64_t { return carry_bytes; };
+        // The last output plane of the rows so far: the seed of the next row's axis-0 sum.
+        // run_pipeline calls apply once per row, for rows in increasing order, from its one
+        // loop, and every call queues on the context's one compute stream; so each row's
+        // kernels find the plane the previous row's kernels left, and the zero fill queued
+        // before the first row comes first. The double-buffered slabs and outputs do not change
+        // that order.
+        DevBuf carry;
+        rop.apply = [&](zt_ctx* c, const void* slab, int64_t in0, int64_t in1, void* o,
+                        int64_t z0, int64_t z1) -> int {
+            if (!carry.p && carry_bytes) {
+                void* stream = nullptr;
+                if (int rc = zt_ctx_get_stream(c, &stream)) return rc;
+                carry.alloc((size_t)carry_bytes);
+                HIPCHK(hipMemsetAsync(carry.p, 0, (size_t)carry_bytes,
+                                      static_cast<hipStream_t>(stream)));
+            }
+            std::vector<int64_t> bshape(shape);
+            bshape[0] = in1 - in0;
+            return zt_summed_area_table_apply_ndarray(c, din, slab, bshape.data(), nd, dt, o,
+                                                      carry.p);
+        };
+        run_pipeline(in, out, device, 0, -1, nthreads, rop, stats);
+        if (flags & ZT_STORE_FINISH_OUTPUT) out.store_metadata();
+        return ZT_OK;
+    } catch (const std::exception& e) {
+        return report(e);
+    }
+}
+
 int zt_store_downsample_gaussian(const char* in_path, const char* out_path, const int64_t* stride,
                                  const float* sigma, const int64_t* kernel_half_size,
                                  int dtype_out, const char* encoding_json, int device,

@@ -1073,6 +1073,79 @@ int zt_gradient_magnitude_apply_array(zt_ctx* ctx, int dtype_in, const void* in,
                                   op);
 }
 
+// ---- summed-area table (summed_area_table.rs) ------------------------------------------------
+
+namespace {
+
+// SummedAreaTable::apply on a C-order block: the scans run last axis to first; the first reads
+// `in` (casting to dtype_out), the others work on `out` in place. `carry` seeds the axis-0 scan
+// and receives its last plane.
+int run_summed_area_table(zt_ctx* ctx, int dtype_in, const void* in, const int64_t* shape,
+                          int ndim, int dtype_out, void* out, void* carry) {
+    if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev0, ctx->cur));
+    for (int axis = ndim - 1; axis >= 0; --axis) {
+        const bool first = axis == ndim - 1;
+        void* seed = axis == 0 ? carry : nullptr;
+        hipError_t e = zt::launch_sat_pass(first ? in : out, first ? dtype_in : dtype_out, out,
+                                           dtype_out, numel(shape, axis), shape[axis],
+                                           numel(shape + axis + 1, ndim - axis - 1), seed, seed,
+                                           ctx->cur);
+        if (e != hipSuccess) return hip_fail(e, "summed area table pass launch");
+    }
+    if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev1, ctx->cur));
+    return ZT_OK;
+}
+
+}  // namespace
+
+int zt_summed_area_table_is_compatible(int dtype_in, int dtype_out) {
+    // summed_area_table.rs:110-134: every listed type is accepted for input and output.
+    return dtypes_ok(dtype_in, dtype_out);
+}
+
+int zt_summed_area_table_memory_per_chunk(int dtype_in, int dtype_out, const int64_t* chunk_shape,
+                                          int ndim, uint64_t* bytes) {
+    if (int rc = dtypes_ok(dtype_in, dtype_out)) return rc;
+    if (int rc = check_shape(chunk_shape, ndim, "chunk_shape")) return rc;
+    if (!bytes) return fail(ZT_ERR_INVALID_PARAMETERS, "null pointer");
+    // summed_area_table.rs:136-142 (sic): one element of each type, whatever the chunk shape
+    *bytes = zt::dtype_size(dtype_in) + zt::dtype_size(dtype_out);
+    return ZT_OK;
+}
+
+int zt_summed_area_table_apply_ndarray(zt_ctx* ctx, int dtype_in, const void* in,
+                                       const int64_t* shape, int ndim, int dtype_out, void* out,
+                                       void* carry) {
+    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = dtypes_ok(dtype_in, dtype_out)) return rc;
+    if (int rc = check_shape(shape, ndim, "shape")) return rc;
+    if (numel(shape, ndim) == 0) return ZT_OK;
+    if (!in || !out) return fail(ZT_ERR_INVALID_PARAMETERS, "null data pointer");
+    if (in == out) return fail(ZT_ERR_INVALID_PARAMETERS, "input and output must differ");
+    DeviceGuard g(ctx->device);
+    return run_summed_area_table(ctx, dtype_in, in, shape, ndim, dtype_out, out, carry);
+}
+
+int zt_summed_area_table_apply_array(zt_ctx* ctx, int dtype_in, const void* in, int dtype_out,
+                                     void* out, const int64_t* shape, int ndim,
+                                     const int64_t* chunk_shape) {
+    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = dtypes_ok(dtype_in, dtype_out)) return rc;
+    if (int rc = check_shape(shape, ndim, "shape")) return rc;
+    if (!chunk_shape) return fail(ZT_ERR_INVALID_PARAMETERS, "null chunk_shape");
+    for (int d = 0; d < ndim; ++d)
+        if (chunk_shape[d] <= 0)
+            return fail(ZT_ERR_INVALID_PARAMETERS, "chunk extent must be positive");
+    if (numel(shape, ndim) == 0) return ZT_OK;
+    if (!in || !out) return fail(ZT_ERR_INVALID_PARAMETERS, "null data pointer");
+    if (in == out) return fail(ZT_ERR_INVALID_PARAMETERS, "input and output must differ");
+    // The reference carries each chunk's last plane into the next chunk along the scanned axis
+    // (summed_area_table.rs:69, :94-97): the same left-to-right fold as one lane over the whole
+    // axis, so the chunk grid does not enter the result.
+    DeviceGuard g(ctx->device);
+    return run_summed_area_table(ctx, dtype_in, in, shape, ndim, dtype_out, out, nullptr);
+}
+
 // ---- downsample ------------------------------------------------------------------------------
 
 int zt_downsample_is_compatible(int dtype_in, int dtype_out, int discrete) {

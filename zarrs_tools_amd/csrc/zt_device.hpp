@@ -11,6 +11,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace zt {
 
 enum DType : int {
@@ -200,6 +202,31 @@ template <> __device__ inline double from_f64<double>(double x) { return x; }
 template <> __device__ inline bf16_t from_f64<bf16_t>(double x) { return bf16_t{f64_to_bf16_bits(x)}; }
 template <> __device__ inline f16_t from_f64<f16_t>(double x) { return f16_t{f64_to_f16_bits(x)}; }
 #undef ZT_SAT
+
+// ---- TIn.as_() -> TOut for every pair (reencode.rs:58-77, summed_area_table.rs:81) ----------------
+// num-traits 0.2.19 AsPrimitive and half 2.6.0's impls: a half type converts through f32 (to f64
+// directly), any type converts to a half type through `as f32` and from_f32 (f64 through
+// from_f64); float -> int saturates (NaN -> 0); int -> int wraps; int -> float rounds to nearest.
+template <typename T> constexpr bool kIsHalf = std::is_same_v<T, bf16_t> || std::is_same_v<T, f16_t>;
+template <typename T> constexpr bool kIsFloat = std::is_same_v<T, float> || std::is_same_v<T, double>;
+
+template <typename TI, typename TO>
+__device__ inline TO as_cast(TI v) {
+    if constexpr (std::is_same_v<TI, TO>) {
+        return v;
+    } else if constexpr (kIsHalf<TI>) {
+        if constexpr (std::is_same_v<TO, double>) return Elem<TI>::to_f64(v);
+        else return as_cast<float, TO>(Elem<TI>::to_f32(v));
+    } else if constexpr (kIsHalf<TO>) {
+        if constexpr (std::is_same_v<TI, double>) return from_f64<TO>(v);
+        else return from_f32<TO>(as_cast<TI, float>(v));
+    } else if constexpr (kIsFloat<TI> && !kIsFloat<TO>) {
+        if constexpr (std::is_same_v<TI, float>) return from_f32<TO>(v);
+        else return from_f64<TO>(v);
+    } else {
+        return (TO)v;  // int -> int (two's complement wrap), int -> float (RNE), f32 <-> f64
+    }
+}
 
 // Dispatch a runtime dtype code to a C++ element type (Bool is processed as u8, like the
 // reference's `(Bool, u8)` dispatch arms).

@@ -150,6 +150,19 @@ hipError_t launch_gm_accumulate(float* g, const float* sq, int64_t total, bool f
 hipError_t launch_gm_finish(const float* g, int dtype_out, void* out, const NdGeom& geom,
                             hipStream_t s);
 
+// Summed-area table (sat.hip; summed_area_table.rs:47-106): one inclusive running sum along the
+// axis of extent n of a C-order array outer x n x inner, `element += acc` left to right in
+// dtype_out, one thread per lane. in != out: the first pass (inner == 1 only), which casts
+// dtype_in -> dtype_out on the way in; in == out (dtype_in == dtype_out): in place. seed / last:
+// nullptr or outer * inner dtype_out values, the lanes' seeds (zero when null) and where their
+// last values go; they may be the same buffer.
+constexpr int kSatThreads = 256;  // threads per workgroup; lanes per workgroup when inner > 1
+constexpr int kSatRows = 256;     // rows per workgroup of the x scan (inner == 1)
+constexpr int kSatTileW = 32;     // x tile width of the x scan, output types of up to 4 bytes
+constexpr int kSatTileW8 = 16;    // ... of 8 bytes
+hipError_t launch_sat_pass(const void* in, int dtype_in, void* out, int dtype_out, int64_t outer,
+                           int64_t n, int64_t inner, const void* seed, void* last, hipStream_t s);
+
 // Synthetic inputs
 hipError_t launch_synth_step_noise_f32(float* out, int64_t n, int64_t plane, int64_t nx_row,
                                        int64_t nx_global, int64_t z0, uint64_t seed,

@@ -10,6 +10,8 @@ Names, argument meaning and error behaviour follow LDeakin/zarrs_tools 0.7.2:
   - ``GradientMagnitude`` <- src/filter/filters/gradient_magnitude.rs (GradientMagnitude::new(
     operator, chunk_limit), apply_chunk :68, apply_ndarray :109, is_compatible :151,
     memory_per_chunk :177, apply :197)
+  - ``SummedAreaTable`` <- src/filter/filters/summed_area_table.rs (SummedAreaTable::new(
+    chunk_limit), apply_dim :47, is_compatible :110, memory_per_chunk :136, apply :144)
   - ``ArraySubsetOverlap`` <- src/filter/array_subset_overlap.rs:4-52
 Arrays are device-resident torch tensors (torch is used only for device memory and streams);
 every computation runs in libzarrs_tools_amd.so through the C ABI.
@@ -430,6 +432,69 @@ class GradientMagnitude:
             ctx.handle, DTYPES[input.dtype], _ptr(input.data.contiguous()), DTYPES[output.dtype],
             _ptr(output.data), i64_array(input.shape), nd, i64_array(output.chunk_shape),
             self._op))
+
+
+class SummedAreaTable:
+    """summed_area_table.rs:38-254 — `SummedAreaTable::new(chunk_limit)`: an inclusive running
+    sum along every axis, last axis first, in the output type (integers wrap; floats keep the
+    reference's left-to-right order, one rounding per add)."""
+
+    def __init__(self, chunk_limit: Optional[int] = None):
+        self.chunk_limit = chunk_limit
+
+    def name(self) -> str:
+        return "summed area table"
+
+    def is_compatible(self, dtype_in: str, dtype_out: str) -> None:
+        for d in (dtype_in, dtype_out):
+            if d not in DTYPES:
+                raise _abi.UnsupportedDataType(_abi.ERR_UNSUPPORTED_DATA_TYPE,
+                                               f"Unsupported data type {d}")
+        check(lib().zt_summed_area_table_is_compatible(DTYPES[dtype_in], DTYPES[dtype_out]))
+
+    def memory_per_chunk(self, dtype_in: str, dtype_out: str, chunk_shape) -> int:
+        out = ctypes.c_uint64()
+        check(lib().zt_summed_area_table_memory_per_chunk(
+            DTYPES[dtype_in], DTYPES[dtype_out], i64_array(chunk_shape), len(chunk_shape),
+            ctypes.byref(out)))
+        return int(out.value)
+
+    def apply_ndarray(self, v, dtype_out: Optional[str] = None, ctx: Optional[Context] = None,
+                      carry=None):
+        """summed_area_table.rs:47-106 for every axis on a device block; returns the table as
+        `dtype_out` (the input's type by default). `carry`: None, or a contiguous device tensor
+        of v.shape[1:] in the output type: the seed plane of the axis-0 sum on entry (the
+        reference's sum_last between chunks), the last output plane on return."""
+        torch = _torch()
+        v = v.contiguous()
+        ctx = ctx or default_context(v.device.index)
+        dtype_in = dtype_of(v)
+        dtype_out = dtype_out or dtype_in
+        out = torch.empty(tuple(v.shape), dtype=torch_dtype(dtype_out), device=v.device)
+        if carry is not None:
+            if (tuple(carry.shape) != tuple(v.shape[1:]) or carry.dtype != out.dtype
+                    or carry.device != v.device or not carry.is_contiguous()):
+                raise _abi.InvalidParameters(
+                    _abi.ERR_INVALID_PARAMETERS,
+                    "carry must be a contiguous device tensor of the block's shape[1:] in the "
+                    "output type")
+        check(lib().zt_summed_area_table_apply_ndarray(
+            ctx.handle, DTYPES[dtype_in], _ptr(v), i64_array(v.shape), v.dim(),
+            DTYPES[dtype_out], _ptr(out), None if carry is None else _ptr(carry)))
+        return out
+
+    def apply(self, input: DeviceArray, output: DeviceArray,
+              ctx: Optional[Context] = None) -> None:
+        """summed_area_table.rs:144-253 over a device-resident array (one pass per axis; the
+        chunk grid does not enter the result)."""
+        if tuple(output.shape) != tuple(input.shape):
+            raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS,
+                                         "input and output shapes differ")
+        ctx = ctx or default_context(input.data.device.index)
+        check(lib().zt_summed_area_table_apply_array(
+            ctx.handle, DTYPES[input.dtype], _ptr(input.data.contiguous()),
+            DTYPES[output.dtype], _ptr(output.data), i64_array(input.shape), len(input.shape),
+            i64_array(output.chunk_shape)))
 
 
 class Downsample:

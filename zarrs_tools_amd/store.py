@@ -341,6 +341,20 @@ def gradient_magnitude(input_path, output_path, operator: str = "sobel",
     return st.as_dict()
 
 
+def summed_area_table(input_path, output_path, data_type: Optional[str] = None, device: int = 0,
+                      nthreads: int = 0, erase: bool = True, finish: bool = True, encoding=None,
+                      chunk_limit: int = 0) -> dict:
+    """zarrs_filter summed-area-table INPUT OUTPUT [--data-type T] (summed_area_table.rs:144-253)
+    in one read and one write of the store. The chunk rows depend on each other in order, so
+    there is no `rows` range."""
+    set_chunk_limit(chunk_limit)
+    st = _abi.StoreStats()
+    check(lib().zt_store_summed_area_table(_b(input_path), _b(output_path), _dt(data_type),
+                                           _enc(encoding), int(device), int(nthreads),
+                                           _flags(erase, finish), ctypes.byref(st)))
+    return st.as_dict()
+
+
 def downsample_gaussian(input_path, output_path, stride, sigma, kernel_half_size,
                         data_type: Optional[str] = None, device: int = 0, rows=None,
                         nthreads: int = 0, erase: bool = True, finish: bool = True,

@@ -6,12 +6,15 @@ accelerates:
     python -m zarrs_tools_amd.zarrs_filter [--exists erase|exit] [--tmp DIR] [--chunk-limit N]
         [--device D] [RUN_CONFIG.json] [guided-filter IN OUT EPSILON RADIUS [--data-type T]
                                         | downsample IN OUT STRIDE [--discrete] [--data-type T]
-                                        | gaussian IN OUT SIGMA KERNEL_HALF_SIZE [--data-type T]]
+                                        | gaussian IN OUT SIGMA KERNEL_HALF_SIZE [--data-type T]
+                                        | summed-area-table IN OUT [--data-type T]]
 
 * subcommand arguments as GuidedFilterArguments (guided_filter.rs:25-33),
   DownsampleArguments (downsample.rs:20-33, STRIDE comma delimited) and GaussianArguments
   (gaussian.rs:22-30, SIGMA and KERNEL_HALF_SIZE comma delimited, one entry per axis);
-* a JSON run config is a list of {"filter": "guided_filter" | "downsample", "input", "output",
+  summed-area-table takes none of its own (SummedAreaTableArguments, summed_area_table.rs:22-23);
+* a JSON run config is a list of {"filter": "guided_filter" | "downsample" | "gaussian" |
+  "summed_area_table", "input", "output",
   ...args, "data_type"}, with "$name" meaning a named temporary array under --tmp and an omitted
   input meaning the previous filter's output (zarrs_filter.rs:106-138, :338-381);
 * a chain of steps linked only through temporaries (a "$name" or implicit output read by the
@@ -31,8 +34,10 @@ accelerates:
   149-172.
 
 Filters outside the accelerated path (reencode, crop, rescale, clamp, equal, replace_value,
-gradient_magnitude, summed_area_table) are rejected with FilterError::Other: they are out of scope
-(DESIGN.md §1). `--chunk-limit N` bounds the chunks in flight (decoded input rows + output rows
+gradient_magnitude) are rejected with FilterError::Other: they are out of scope (DESIGN.md §1;
+gradient_magnitude runs from the library only). A summed-area table's chunk rows each need the
+previous row's last plane, so with --gpus > 1 that step runs in one process on the first device
+(`rows_splittable`). `--chunk-limit N` bounds the chunks in flight (decoded input rows + output rows
 being computed or encoded, and the host worker threads) at N, down to the pipeline's unit of one
 slab and one output row (guided_filter.rs:251-258); independently the rows held in memory are
 bounded by 80 % of the available host and device memory, failing like calculate_chunk_limit
@@ -53,7 +58,14 @@ import numpy as np
 from . import _abi
 from . import store as S
 
-ON_PATH = ("guided_filter", "downsample", "gaussian")
+ON_PATH = ("guided_filter", "downsample", "gaussian", "summed_area_table")
+
+
+def rows_splittable(name: str) -> bool:
+    """Whether a store step's output chunk rows are independent, so that --gpus > 1 may split
+    them over processes. A summed-area table's rows are not: each row's axis-0 sum starts from
+    the previous row's last plane (summed_area_table.rs:69, :94-97)."""
+    return name != "summed_area_table"
 
 
 def _parse_stride(s: str):
@@ -149,6 +161,10 @@ def build_parser() -> argparse.ArgumentParser:
     gs.add_argument("sigma", type=_parse_floats)
     gs.add_argument("kernel_half_size", type=_parse_stride)
     _add_reencode_args(gs)
+    sa = sub.add_parser("summed-area-table", help="Compute a summed area table (integral image).")
+    sa.add_argument("input")
+    sa.add_argument("output")
+    _add_reencode_args(sa)
     return ap
 
 
@@ -165,6 +181,10 @@ def _steps_from_cli(a) -> list:
         return [{"filter": "gaussian", "input": a.input, "output": a.output, "sigma": a.sigma,
                  "kernel_half_size": a.kernel_half_size, "data_type": a.data_type,
                  "chunk_limit": a.filter_chunk_limit, **_reencode_of(a)}]
+    if a.filter == "summed-area-table":
+        return [{"filter": "summed_area_table", "input": a.input, "output": a.output,
+                 "data_type": a.data_type, "chunk_limit": a.filter_chunk_limit,
+                 **_reencode_of(a)}]
     return []
 
 
@@ -221,6 +241,8 @@ def _step_params(step, info):
                                          "gaussian sigma and kernel_half_size need one entry "
                                          "per axis")
         return F.Gaussian(sigma, half), tuple(info.shape), dt
+    if name == "summed_area_table":
+        return F.SummedAreaTable(), tuple(info.shape), dt
     stride = step.get("stride")
     stride = _parse_stride(stride) if isinstance(stride, str) else stride
     if not stride or len(stride) != info.ndim:
@@ -596,12 +618,21 @@ def run(steps: list, exists: str = "erase", tmp: str | None = None,
             log(f"{i}: gaussian sigma={params['sigma']} "
                 f"kernel_half_size={params['kernel_half_size']} "
                 f"{src} ({info.data_type} {list(info.shape)}) -> {dst}")
+        elif name == "summed_area_table":
+            params = {}
+            log(f"{i}: summed_area_table {src} ({info.data_type} {list(info.shape)}) -> {dst}")
         else:
             params = {"stride": list(f.stride), "discrete": bool(step.get("discrete", False))}
             log(f"{i}: downsample stride={params['stride']} discrete={params['discrete']} "
                 f"{src} ({info.data_type} {list(info.shape)}) -> {dst}")
         params.update(data_type=step.get("data_type"), encoding=enc, chunk_limit=limit)
-        if gpus > 1:
+        if gpus > 1 and not rows_splittable(name):
+            dev0 = (gpu_devices or [0])[0]
+            log(f"   {name}: chunk rows depend on each other in order; one process on device "
+                f"{dev0}, not {gpus}")
+            st = S.summed_area_table(src, dst, data_type=params["data_type"], device=dev0,
+                                     encoding=enc, chunk_limit=limit)
+        elif gpus > 1:
             st = run_rows_parallel(name, src, dst, params, out_shape, gpus, 0,
                                    devices=gpu_devices)
         elif name == "guided_filter":
@@ -612,6 +643,9 @@ def run(steps: list, exists: str = "erase", tmp: str | None = None,
             st = S.gaussian(src, dst, params["sigma"], params["kernel_half_size"],
                             data_type=params["data_type"], device=device, encoding=enc,
                             chunk_limit=limit)
+        elif name == "summed_area_table":
+            st = S.summed_area_table(src, dst, data_type=params["data_type"], device=device,
+                                     encoding=enc, chunk_limit=limit)
         else:
             st = S.downsample(src, dst, params["stride"], discrete=params["discrete"],
                               data_type=params["data_type"], device=device, encoding=enc,
