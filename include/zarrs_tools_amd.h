@@ -280,6 +280,63 @@ int zt_summed_area_table_apply_array(zt_ctx* ctx, int dtype_in, const void* in, 
                                      void* out, const int64_t* shape, int ndim,
                                      const int64_t* chunk_shape);
 
+/* ---- Pointwise filters (src/filter/filters/{reencode,crop,rescale,clamp,equal,replace_value}.rs) */
+
+/* One op of a pointwise program. Op k reads the type op k-1 wrote (the first: the program's
+ * input type) and writes `dtype_out`; every `as` is Rust's (zt_reencode_cast's). Per element v:
+ *   ZT_PW_REENCODE      v as TOut (Reencode::apply_chunk_convert, reencode.rs:58-88; on a sub-box
+ *                       it is Crop::apply_chunk_convert, crop.rs:62-122)
+ *   ZT_PW_RESCALE       x = v as f64; fma(x, multiply, add), one rounding, or with
+ *                       ZT_PW_ADD_FIRST (x + add) * multiply, two roundings; then `as TOut` from
+ *                       f64 (Rescale::apply_elements, rescale.rs:86-122). imm0 / imm1: the f64
+ *                       bits of multiply / add.
+ *   ZT_PW_CLAMP         lo = min as TIn, hi = max as TIn (f64 -> TIn: saturating, NaN -> 0 for
+ *                       integers); v < lo ? lo : (v > hi ? hi : v) (num_traits::clamp: a NaN v
+ *                       passes, a NaN bound disables its side); then `as TOut`
+ *                       (Clamp::apply_elements, clamp.rs:59-70, :150). imm0 / imm1: the f64 bits
+ *                       of min / max.
+ *   ZT_PW_EQUAL         (v == value) as TOut, TOut bool or uint8 (Equal::apply_elements,
+ *                       equal.rs:62-77, :104-109). imm0: `value` as an element of TIn.
+ *   ZT_PW_REPLACE_VALUE v == value ? replace : v as TOut (ReplaceValue::apply_elements,
+ *                       replace_value.rs:82-97, :146-153). imm0: `value` as an element of TIn,
+ *                       imm1: `replace` as an element of TOut.
+ * An element immediate is the element's storage bits, zero-extended (little endian; float16 /
+ * bfloat16 raw bits, bool 0 / 1). `==` compares values: -0.0 == 0.0, NaN equals nothing, 64-bit
+ * integers exactly. */
+enum { ZT_PW_REENCODE = 0, ZT_PW_RESCALE = 1, ZT_PW_CLAMP = 2, ZT_PW_EQUAL = 3,
+       ZT_PW_REPLACE_VALUE = 4 };
+#define ZT_PW_ADD_FIRST 1 /* zt_pointwise_op.flags: RescaleArguments::add_first (rescale.rs:25-35) */
+#define ZT_PW_MAX_OPS 8
+typedef struct zt_pointwise_op {
+    int32_t kind;      /* ZT_PW_* */
+    int32_t dtype_out; /* zt_dtype */
+    uint64_t imm0, imm1;
+    uint32_t flags;
+    uint32_t reserved; /* 0 */
+} zt_pointwise_op;
+
+/* is_compatible of the six filters (reencode.rs:92-118, crop.rs:126-150, rescale.rs:126-150,
+ * clamp.rs:74-98, equal.rs:81-111, replace_value.rs:101-125): all 13 types in and out; equal
+ * writes bool or uint8 only (ZT_ERR_UNSUPPORTED_DATA_TYPE otherwise). kind: ZT_PW_*. */
+int zt_pointwise_is_compatible(int kind, int dtype_in, int dtype_out);
+/* memory_per_chunk: chunk elements x (input + output element size); for ZT_PW_REENCODE (reencode
+ * and crop) the output element size only (reencode.rs:120-126, crop.rs:152-158). */
+int zt_pointwise_memory_per_chunk(int kind, int dtype_in, int dtype_out,
+                                  const int64_t* chunk_shape, int ndim, uint64_t* bytes);
+/* The per-chunk element work of the six filters (Reencode::apply_chunk_convert reencode.rs:58-88,
+ * Crop::apply_chunk_convert crop.rs:62-122, Rescale::apply_chunk rescale.rs:68-122,
+ * Clamp::apply_elements_inplace clamp.rs:59-70 and the `as` of :150, Equal::apply_elements
+ * equal.rs:62-77, ReplaceValue::apply_elements replace_value.rs:82-97) for a program of n_ops in
+ * [1, ZT_PW_MAX_OPS] ops in one launch: the box [sub_start, sub_start + sub_shape) of the C-order
+ * device array `in` (dtype_in, in_shape[ndim]; both NULL: the whole array) goes through the ops
+ * in order, every intermediate `as` performed, into `out` (C order, sub_shape, the last op's
+ * dtype_out), so the result is bit-identical to the ops run one call at a time. The type chain is
+ * validated like zt_pointwise_is_compatible. `in` and `out` need element alignment only. A box
+ * with a zero extent is a no-op. */
+int zt_pointwise_apply_ndarray(zt_ctx* ctx, int dtype_in, const void* in, const int64_t* in_shape,
+                               int ndim, const int64_t* sub_start, const int64_t* sub_shape,
+                               const zt_pointwise_op* ops, int n_ops, void* out);
+
 /* ---- Zarr V3 store -> store path (host storage in and out) ----------------------------------
  * The reference's filters read and write Zarr arrays through zarrs (Array::retrieve_array_subset_
  * ndarray / store_array_subset_ndarray, guided_filter.rs:95-110; zarrs_ome.rs:226-232). These
@@ -412,6 +469,22 @@ int zt_store_gradient_magnitude(const char* in_path, const char* out_path, int d
 int zt_store_summed_area_table(const char* in_path, const char* out_path, int dtype_out,
                                const char* encoding_json, int device, int nthreads, int flags,
                                zt_store_stats* stats);
+/* zarrs_filter reencode / crop / rescale / clamp / equal / replace-value over a store (the apply
+ * chunk loops: reencode.rs:128-218, crop.rs:164-247, rescale.rs:160-239, clamp.rs:108-211,
+ * equal.rs:125-214, replace_value.rs:135-240), or several of them in one pass: the program
+ * `ops` (zt_pointwise_apply_ndarray) runs on every output chunk row, no halo. crop_offset /
+ * crop_shape (both NULL: no crop; one entry per axis, inside the input or
+ * ZT_ERR_INVALID_PARAMETERS) make the output the box's shape (Crop::output_shape,
+ * crop.rs:160-162), output element i reading input element crop_offset + i
+ * (get_input_output_subset, crop.rs:62-76). The output array's data type (dtype_out /
+ * encoding_json, as zt_store_guided_filter) must be the last op's dtype_out; missing input
+ * chunks read as the fill value and go through the ops like any element. Rows as
+ * zt_store_guided_filter. */
+int zt_store_pointwise(const char* in_path, const char* out_path, int dtype_out,
+                       const char* encoding_json, const zt_pointwise_op* ops, int n_ops,
+                       const int64_t* crop_offset, const int64_t* crop_shape, int device,
+                       int64_t row_begin, int64_t row_end, int nthreads, int flags,
+                       zt_store_stats* stats);
 /* One zarrs_ome level with --gaussian-sigma (apply_chunk_continuous_gaussian, zarrs_ome.rs:
  * 236-271): the Gaussian of each downsample input subset (plus its kernel_half_size halo), then
  * the mean downsample of that f32 block to the level's data type. */

@@ -9,6 +9,9 @@ kernel_half_size 1 on the same volume (its yardstick), windows of at least half 
 `--only sat`: the summed-area table on 1024^3 float32 -> float32 and uint16 -> uint64, each
 alternated with the reencode cast of the same type pair on the same volume (one read and one
 write per voxel: the streaming yardstick).
+`--only pointwise`: the per-element filters (reencode, crop, rescale, clamp, equal, replace_value)
+on 1024^3, each single launch alternated with the reencode cast of the same type pair, and the
+fused rescale -> clamp -> equal chain against its three single launches.
 
 Algorithmic bytes: pyramid = level 0 read once + every level written once (2 B per u16
 element; the fused launches never read an intermediate level back); Gaussian = 4 B read + 4 B written per voxel (the separable passes' intermediates are
@@ -265,6 +268,148 @@ def bench_sat(n, din, dout, rounds=5, window_s=0.5):
             "ratio_to_yardstick_per_pass_byte": round((s["ms"] / act) / (y_["ms"] / alg), 4)}
 
 
+def bench_pointwise(n, rounds=5, window_s=0.25):
+    """The per-element filters on n^3, device-resident, one launch each (pointwise.hip): every
+    single op on uint16 -> uint16, float32 -> float32 and uint16 -> uint8 (equal: uint8 -> bool),
+    alternated in one run with zt_reencode_cast of the same type pair on the same volume (the
+    scalar cast kernel, the yardstick); then the documented chain rescale(0.01275, 0) -> uint8,
+    clamp(2, 5), equal(5) -> bool as one fused launch against its three single launches,
+    alternated. Windows as bench_gradient. Bytes per element: size(in) + size(out) of the
+    launch. One JSON line per group; a sampled block of every result is checked against the
+    restatement (tests/pw_ref.py)."""
+    import math
+    import numpy as np
+    import torch
+    import zarrs_tools_amd as zt
+    from zarrs_tools_amd import _abi
+    from zarrs_tools_amd.filter import DTYPES, _ptr
+    from tests import pw_ref as R
+    from tests.gpu_util import from_dev
+    ctx = zt.default_context(0)
+    stream = torch.cuda.current_stream()
+    u16 = zt.synth_u16((n, n, n))
+    f32 = zt.synth_step_noise_f32((n, n, n))
+    u8 = zt.PointwiseProgram([zt.Rescale(0.01275, 0.0)], "uint16", ["uint8"],
+                             u16.shape).apply_ndarray(u16, ctx)
+    src = {"uint16": u16, "float32": f32, "uint8": u8}
+    m = 4096  # the sampled check: the first m elements (a crop: its first row's first m)
+
+    def measure(ops):
+        reps = {}
+        for k, fn in ops.items():  # warm-up, then calls per window until it lasts window_s
+            r = 4
+            while True:
+                t = timed(fn, stream, r)
+                if t * r >= window_s * 1e3:
+                    break
+                r = math.ceil(window_s * 1e3 / t * 1.05) + 1
+            reps[k] = r
+        ms = {k: [] for k in ops}
+        for _ in range(rounds):
+            for k, fn in ops.items():
+                ms[k].append(timed(fn, stream, reps[k]))
+        return ms, reps
+
+    def line(v, r, nbytes):
+        v = sorted(v)
+        med = v[len(v) // 2]
+        gbs = nbytes / (med / 1e3) / 1e9
+        return {"ms": round(med, 4), "ms_min": round(v[0], 4), "ms_max": round(v[-1], 4),
+                "spread": round((v[-1] - v[0]) / med, 4), "calls_per_window": r,
+                "bytes": nbytes, "GB/s": round(gbs, 1),
+                "hbm_frac": round(gbs / HBM_PEAK_GBS, 4)}
+
+    def single(din, dout, name, filt, ref_kw):
+        x = src[din]
+        prog = zt.PointwiseProgram([filt], din, [dout], x.shape)
+        y = torch.empty(tuple(prog.shape), dtype=zt.torch_dtype(dout), device=x.device)
+        prog.run(x, y, ctx)
+        torch.cuda.synchronize()
+        if name == "crop":
+            o = prog.offset
+            xs = from_dev(x[o[0], o[1], o[2]:o[2] + min(m, prog.shape[2])], din)
+            ref = R.reencode(xs, din, dout)
+        else:
+            ref = R.program(from_dev(x.reshape(-1)[:m], din), din, [(name, dout, ref_kw)])
+        got = from_dev(y.reshape(-1)[:ref.size], dout)
+        ok = bool(np.array_equal(got.view(np.uint8), ref.view(np.uint8)))
+        nbytes = int(y.numel()) * (x.element_size() + y.element_size())
+        return (lambda: prog.run(x, y, ctx)), ok, nbytes, y
+
+    out = []
+    groups = [("uint16", "uint16", 5), ("float32", "float32", 5.0), ("uint16", "uint8", 5),
+              ("uint8", "bool", 5)]
+    for din, dout, five in groups:
+        x = src[din]
+        cases = {"equal": (zt.Equal(five), dict(value=five))} if dout == "bool" else {
+            "reencode": (zt.Reencode(), {}),
+            "crop": (zt.Crop((8, 8, 8), (n - 16,) * 3), {}),
+            "rescale": (zt.Rescale(0.01275, 0.5), dict(multiply=0.01275, add=0.5)),
+            "clamp": (zt.Clamp(2, 500), dict(lo=2.0, hi=500.0)),
+            "replace_value": (zt.ReplaceValue(five, 0), dict(value=five, replace=0))}
+        ops, meta, keep = {}, {}, []
+        for name, (filt, kw) in cases.items():
+            fn, ok, nbytes, y = single(din, dout, name, filt, kw)
+            ops[name], meta[name] = fn, (ok, nbytes)
+            keep.append(y)
+        yc = torch.empty(tuple(x.shape), dtype=zt.torch_dtype(dout), device=x.device)
+
+        def cast(x=x, yc=yc, din=din, dout=dout):
+            _abi.check(_abi.lib().zt_reencode_cast(ctx.handle, DTYPES[din], _ptr(x),
+                                                   DTYPES[dout], _ptr(yc), n ** 3))
+
+        ops["cast"] = cast
+        ms, reps = measure(ops)
+        cast_bytes = n ** 3 * (x.element_size() + yc.element_size())
+        yard = line(ms["cast"], reps["cast"], cast_bytes)
+        res = {"op": f"pointwise {din} -> {dout} (device-resident), single launches",
+               "config": {"shape": [n] * 3, "rounds": rounds, "window_s": window_s},
+               "yardstick": {"op": f"reencode cast {din} -> {dout} (zt_reencode_cast), same "
+                                   "volume, windows alternated", **yard}, "ops": {}}
+        for name in cases:
+            ln = line(ms[name], reps[name], meta[name][1])
+            ln["parity_bit_exact_sample"] = meta[name][0]
+            ln["ratio_to_cast_per_byte"] = round((ln["ms"] / ln["bytes"]) /
+                                                 (yard["ms"] / yard["bytes"]), 4)
+            res["ops"][name] = ln
+        out.append(res)
+        del keep, yc
+        torch.cuda.empty_cache()
+    # the fused chain against its three single launches
+    fs = [zt.Rescale(0.01275, 0.0), zt.Clamp(2, 5), zt.Equal(5)]
+    ts = ["uint8", "uint8", "bool"]
+    a = torch.empty((n, n, n), dtype=torch.uint8, device=u16.device)
+    b = torch.empty_like(a)
+    c = torch.empty_like(a)
+    d = torch.empty_like(a)
+    p1 = zt.PointwiseProgram(fs[:1], "uint16", ts[:1], u16.shape)
+    p2 = zt.PointwiseProgram(fs[1:2], "uint8", ts[1:2], u16.shape)
+    p3 = zt.PointwiseProgram(fs[2:], "uint8", ts[2:], u16.shape)
+    pf = zt.PointwiseProgram(fs, "uint16", ts, u16.shape)
+    ops = {"fused": lambda: pf.run(u16, d, ctx), "rescale": lambda: p1.run(u16, a, ctx),
+           "clamp": lambda: p2.run(a, b, ctx), "equal": lambda: p3.run(b, c, ctx)}
+    for fn in ops.values():
+        fn()
+    torch.cuda.synchronize()
+    ref = R.program(from_dev(u16.reshape(-1)[:m], "uint16"), "uint16", [
+        ("rescale", "uint8", dict(multiply=0.01275, add=0.0)),
+        ("clamp", "uint8", dict(lo=2.0, hi=5.0)), ("equal", "bool", dict(value=5))])
+    ok = bool(np.array_equal(from_dev(d.reshape(-1)[:m], "uint8"), ref) and
+              torch.equal(c, d))
+    ms, reps = measure(ops)
+    nb = {"fused": 3, "rescale": 3, "clamp": 2, "equal": 2}
+    lines = {k: line(ms[k], reps[k], n ** 3 * nb[k]) for k in ops}
+    sum_ms = sum(lines[k]["ms"] for k in ("rescale", "clamp", "equal"))
+    out.append({"op": "pointwise chain rescale -> uint8, clamp, equal -> bool on uint16 "
+                      "(device-resident): one fused launch against three",
+                "config": {"shape": [n] * 3, "rounds": rounds, "window_s": window_s},
+                "parity_bit_exact_sample": ok, "fused_equals_unfused": bool(torch.equal(c, d)),
+                "launches": lines, "unfused_sum_ms": round(sum_ms, 4),
+                "fused_over_unfused": round(lines["fused"]["ms"] / sum_ms, 4),
+                "fused_is_faster": bool(lines["fused"]["ms"] < sum_ms)})
+    return out
+
+
 def bench_guided4d(shape, chunk, radius, reps):
     """Config T per GPU: a (T, Z, Y, X) f32 time-series share, chunks
     (4, 256, 256, 256), eps 2500. 4-D arrays take the separable per-axis path."""
@@ -399,6 +544,9 @@ def main():
     if "sat" in only:  # each with its reencode-cast yardstick, alternated
         for din, dout in (("float32", "float32"), ("uint16", "uint64")):
             print(json.dumps(bench_sat(a.gaussian_size, din, dout)), flush=True)
+    if "pointwise" in only:  # each with its reencode-cast yardstick, alternated
+        for res in bench_pointwise(a.gaussian_size):
+            print(json.dumps(res), flush=True)
 
 
 if __name__ == "__main__":

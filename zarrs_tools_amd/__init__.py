@@ -12,12 +12,19 @@ lib()  # fail at import time if the native library is absent
 from .filter import (  # noqa: E402
     ArraySubset,
     ArraySubsetOverlap,
+    Clamp,
     Context,
+    Crop,
     DeviceArray,
     Downsample,
+    Equal,
     Gaussian,
     GradientMagnitude,
     GuidedFilter,
+    PointwiseProgram,
+    Reencode,
+    ReplaceValue,
+    Rescale,
     SummedAreaTable,
     default_context,
     dtype_of,
@@ -34,6 +41,7 @@ __all__ = [
     "ArraySubset", "ArraySubsetOverlap", "Context", "DeviceArray", "Downsample", "DTYPES",
     "FilterError", "Gaussian", "GradientMagnitude", "GuidedFilter", "InvalidParameters", "SlabAssignment", "SummedAreaTable",
     "UnsupportedDataType",
+    "Clamp", "Crop", "Equal", "PointwiseProgram", "Reencode", "ReplaceValue", "Rescale",
     "default_context", "dtype_of", "lib", "octant_assignment", "OctantAssignment", "pyramid",
     "pyramid_level_shapes", "slab_assignment",
     "synth_step_noise_f32", "synth_u16", "synth_box", "torch_dtype",

@@ -67,6 +67,19 @@ _lib = None
 # ZT_GM_* (GradientMagnitudeOperator, gradient_magnitude.rs:24-29)
 GM_OPERATORS = {"sobel": 0, "central_difference": 1}
 
+# ZT_PW_* (zt_pointwise_op.kind); crop is a reencode of a sub-box
+PW_REENCODE, PW_RESCALE, PW_CLAMP, PW_EQUAL, PW_REPLACE_VALUE = range(5)
+PW_ADD_FIRST = 1
+PW_MAX_OPS = 8
+
+
+class PointwiseOp(ctypes.Structure):
+    """zt_pointwise_op (include/zarrs_tools_amd.h)."""
+    _fields_ = [("kind", ctypes.c_int32), ("dtype_out", ctypes.c_int32),
+                ("imm0", ctypes.c_uint64), ("imm1", ctypes.c_uint64),
+                ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
 # flags of the store filters
 STORE_ERASE_OUTPUT_METADATA = 1
 STORE_FINISH_OUTPUT = 2
@@ -180,6 +193,15 @@ def lib() -> ctypes.CDLL:
                                                c_int),
         "zt_summed_area_table_apply_array": ([vp, c_int, vp, c_int, vp, i64p, c_int, i64p],
                                              c_int),
+        "zt_pointwise_is_compatible": ([c_int, c_int, c_int], c_int),
+        "zt_pointwise_memory_per_chunk": ([c_int, c_int, c_int, i64p, c_int,
+                                           ctypes.POINTER(ctypes.c_uint64)], c_int),
+        "zt_pointwise_apply_ndarray": ([vp, c_int, vp, i64p, c_int, i64p, i64p,
+                                        ctypes.POINTER(PointwiseOp), c_int, vp], c_int),
+        "zt_store_pointwise": ([ctypes.c_char_p, ctypes.c_char_p, c_int, ctypes.c_char_p,
+                                ctypes.POINTER(PointwiseOp), c_int, i64p, i64p, c_int,
+                                ctypes.c_int64, ctypes.c_int64, c_int, c_int,
+                                ctypes.POINTER(StoreStats)], c_int),
         "zt_synth_step_noise_f32": ([vp, vp, i64p, c_int, i64p, ctypes.c_int64, ctypes.c_uint64],
                                     c_int),
         "zt_synth_u16": ([vp, vp, i64p, c_int, i64p, ctypes.c_int64, ctypes.c_uint64], c_int),

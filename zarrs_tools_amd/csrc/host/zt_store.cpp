@@ -1349,6 +1349,73 @@ int zt_store_summed_area_table(const char* in_path, const char* out_path, int dt
     }
 }
 
+int zt_store_pointwise(const char* in_path, const char* out_path, int dtype_out,
+                       const char* encoding_json, const zt_pointwise_op* ops, int n_ops,
+                       const int64_t* crop_offset, const int64_t* crop_shape, int device,
+                       int64_t row_begin, int64_t row_end, int nthreads, int flags,
+                       zt_store_stats* stats) {
+    try {
+        if (!in_path || !out_path || !ops)
+            return zt::set_last_error(ZT_ERR_INVALID_PARAMETERS, "null argument");
+        if (n_ops < 1 || n_ops > ZT_PW_MAX_OPS)
+            return zt::set_last_error(ZT_ERR_INVALID_PARAMETERS,
+                                      "a pointwise program has 1 to 8 ops");
+        if ((crop_offset == nullptr) != (crop_shape == nullptr))
+            return zt::set_last_error(ZT_ERR_INVALID_PARAMETERS,
+                                      "crop offset and shape go together");
+        Array in = Array::open(in_path);
+        const int nd = in.ndim();
+        // Crop::output_shape (crop.rs:160-162); the box must lie inside the input
+        std::vector<int64_t> off(nd, 0), oshape(in.shape);
+        if (crop_offset)
+            for (int d = 0; d < nd; ++d) {
+                off[d] = crop_offset[d];
+                oshape[d] = crop_shape[d];
+                if (off[d] < 0 || oshape[d] < 0 || off[d] + oshape[d] > in.shape[d])
+                    return zt::set_last_error(ZT_ERR_INVALID_PARAMETERS,
+                                              "crop offset + shape beyond the input array");
+            }
+        // the program's type chain first: an invalid program sets nothing up
+        int chain = in.dtype;
+        for (int k = 0; k < n_ops; ++k) {
+            if (int rc = zt_pointwise_is_compatible(ops[k].kind, chain, ops[k].dtype_out))
+                return rc;
+            chain = ops[k].dtype_out;
+        }
+        Array out = build_output(in, out_path, dtype_out, oshape, encoding_json);
+        const int dt = out.dtype;
+        if (chain != dt)
+            return zt::set_last_error(ZT_ERR_INVALID_PARAMETERS,
+                                      "the last op's data type is not the output array's");
+        if (flags & ZT_STORE_ERASE_OUTPUT_METADATA) out.erase_metadata();
+        const int64_t off0 = off[0];
+        RowOp rop;
+        rop.input_planes = [&](int64_t z0, int64_t z1, int64_t& a, int64_t& b) {
+            a = z0 + off0;  // no halo: get_input_output_subset (crop.rs:62-76)
+            b = z1 + off0;
+        };
+        const std::vector<int64_t> shape = in.shape;
+        const int din = in.dtype;
+        rop.apply = [&](zt_ctx* c, const void* slab, int64_t in0, int64_t in1, void* o,
+                        int64_t z0, int64_t z1) -> int {
+            // the slab holds whole input planes; the kernel reads the rows' box out of it
+            std::vector<int64_t> bshape(shape), start(off), sub(oshape);
+            bshape[0] = in1 - in0;
+            start[0] = 0;
+            sub[0] = z1 - z0;
+            return zt_pointwise_apply_ndarray(c, din, slab, bshape.data(), nd, start.data(),
+                                              sub.data(), ops, n_ops, o);
+        };
+        bool empty = false;
+        for (int d = 0; d < nd; ++d) empty = empty || oshape[d] == 0;
+        if (!empty) run_pipeline(in, out, device, row_begin, row_end, nthreads, rop, stats);
+        if (flags & ZT_STORE_FINISH_OUTPUT) out.store_metadata();
+        return ZT_OK;
+    } catch (const std::exception& e) {
+        return report(e);
+    }
+}
+
 int zt_store_downsample_gaussian(const char* in_path, const char* out_path, const int64_t* stride,
                                  const float* sigma, const int64_t* kernel_half_size,
                                  int dtype_out, const char* encoding_json, int device,

@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -1144,6 +1145,190 @@ int zt_summed_area_table_apply_array(zt_ctx* ctx, int dtype_in, const void* in, 
     // axis, so the chunk grid does not enter the result.
     DeviceGuard g(ctx->device);
     return run_summed_area_table(ctx, dtype_in, in, shape, ndim, dtype_out, out, nullptr);
+}
+
+// ---- pointwise filters (reencode.rs, crop.rs, rescale.rs, clamp.rs, equal.rs, replace_value.rs) --
+
+namespace {
+
+// f64 `as` an integer type on the host: saturating, NaN -> 0 (clamp.rs:59-70's `min as TIn`)
+extern "C++" {
+template <typename T>
+T sat_from_f64(double x) {
+    if (!(x == x)) return (T)0;
+    if (x <= (double)std::numeric_limits<T>::min()) return std::numeric_limits<T>::min();
+    if (x >= (double)std::numeric_limits<T>::max()) return std::numeric_limits<T>::max();
+    return (T)x;
+}
+}
+
+// The class value (zt_kernels.hpp, PwClass) of the f64 `x as dtype`, as bits.
+uint64_t class_bits_from_f64(double x, int dtype) {
+    switch (dtype) {
+    case ZT_BOOL: case ZT_UINT8: return sat_from_f64<uint8_t>(x);
+    case ZT_UINT16: return sat_from_f64<uint16_t>(x);
+    case ZT_UINT32: return sat_from_f64<uint32_t>(x);
+    case ZT_UINT64: return sat_from_f64<uint64_t>(x);
+    case ZT_INT8: return (uint32_t)(int32_t)sat_from_f64<int8_t>(x);
+    case ZT_INT16: return (uint32_t)(int32_t)sat_from_f64<int16_t>(x);
+    case ZT_INT32: return (uint32_t)sat_from_f64<int32_t>(x);
+    case ZT_INT64: return (uint64_t)sat_from_f64<int64_t>(x);
+    case ZT_BFLOAT16: return zt::f2u(zt::bf16_bits_to_f32(zt::f64_to_bf16_bits(x)));
+    case ZT_FLOAT16: return zt::f2u(zt::f16_bits_to_f32(zt::f64_to_f16_bits(x)));
+    case ZT_FLOAT32: return zt::f2u((float)x);
+    default: return zt::d2u(x);
+    }
+}
+
+// The class value of an element given as its storage bits (zero-extended little endian).
+uint64_t class_bits_from_storage(uint64_t bits, int dtype) {
+    switch (dtype) {
+    case ZT_BOOL: case ZT_UINT8: return bits & 0xFFu;
+    case ZT_UINT16: return bits & 0xFFFFu;
+    case ZT_UINT32: return bits & 0xFFFFFFFFu;
+    case ZT_INT8: return (uint32_t)(int32_t)(int8_t)bits;
+    case ZT_INT16: return (uint32_t)(int32_t)(int16_t)bits;
+    case ZT_INT32: return bits & 0xFFFFFFFFu;
+    case ZT_BFLOAT16: return zt::f2u(zt::bf16_bits_to_f32((uint16_t)bits));
+    case ZT_FLOAT16: return zt::f2u(zt::f16_bits_to_f32((uint16_t)bits));
+    case ZT_FLOAT32: return bits & 0xFFFFFFFFu;
+    default: return bits;  // int64, uint64, float64
+    }
+}
+
+int pointwise_pair_ok(int kind, int dtype_in, int dtype_out) {
+    if (kind < ZT_PW_REENCODE || kind > ZT_PW_REPLACE_VALUE)
+        return fail(ZT_ERR_INVALID_PARAMETERS, "unknown pointwise op kind %d", kind);
+    if (int rc = dtypes_ok(dtype_in, dtype_out)) return rc;
+    // equal.rs:104-109: the output is bool or uint8
+    if (kind == ZT_PW_EQUAL && dtype_out != ZT_BOOL && dtype_out != ZT_UINT8)
+        return fail(ZT_ERR_UNSUPPORTED_DATA_TYPE, "Unsupported data type %s (equal writes bool "
+                    "or uint8)", dtype_name(dtype_out));
+    return ZT_OK;
+}
+
+// Validate the type chain and translate the ABI ops to the kernel's program.
+int build_pointwise_program(int dtype_in, const zt_pointwise_op* ops, int n_ops,
+                            zt::PwProgram* prog) {
+    if (!ops) return fail(ZT_ERR_INVALID_PARAMETERS, "null ops");
+    if (n_ops < 1 || n_ops > ZT_PW_MAX_OPS)
+        return fail(ZT_ERR_INVALID_PARAMETERS, "a pointwise program has 1 to %d ops, not %d",
+                    ZT_PW_MAX_OPS, n_ops);
+    std::memset(prog, 0, sizeof(*prog));
+    prog->n_ops = n_ops;
+    prog->dt_in = dtype_in;
+    int dt = dtype_in;
+    for (int k = 0; k < n_ops; ++k) {
+        const zt_pointwise_op& o = ops[k];
+        if (int rc = pointwise_pair_ok(o.kind, dt, o.dtype_out)) return rc;
+        zt::PwOp& p = prog->ops[k];
+        p.dt_out = o.dtype_out;
+        switch (o.kind) {
+        case ZT_PW_REENCODE: p.kind = zt::kPwCast; break;
+        case ZT_PW_RESCALE:
+            p.kind = zt::kPwRescale;
+            p.flags = (o.flags & ZT_PW_ADD_FIRST) ? zt::kPwAddFirst : 0;
+            p.a = o.imm0;
+            p.b = o.imm1;
+            break;
+        case ZT_PW_CLAMP: {
+            double lo, hi;
+            std::memcpy(&lo, &o.imm0, 8);
+            std::memcpy(&hi, &o.imm1, 8);
+            p.kind = zt::kPwClamp;
+            p.a = class_bits_from_f64(lo, dt);
+            p.b = class_bits_from_f64(hi, dt);
+            break;
+        }
+        case ZT_PW_EQUAL:
+            p.kind = zt::kPwEqual;
+            p.a = class_bits_from_storage(o.imm0, dt);
+            break;
+        default:
+            p.kind = zt::kPwReplace;
+            p.a = class_bits_from_storage(o.imm0, dt);
+            p.b = class_bits_from_storage(o.imm1, o.dtype_out);
+            break;
+        }
+        dt = o.dtype_out;
+    }
+    return ZT_OK;
+}
+
+}  // namespace
+
+int zt_pointwise_is_compatible(int kind, int dtype_in, int dtype_out) {
+    return pointwise_pair_ok(kind, dtype_in, dtype_out);
+}
+
+int zt_pointwise_memory_per_chunk(int kind, int dtype_in, int dtype_out,
+                                  const int64_t* chunk_shape, int ndim, uint64_t* bytes) {
+    if (int rc = pointwise_pair_ok(kind, dtype_in, dtype_out)) return rc;
+    if (int rc = check_shape(chunk_shape, ndim, "chunk_shape")) return rc;
+    if (!bytes) return fail(ZT_ERR_INVALID_PARAMETERS, "null pointer");
+    // reencode.rs:120-126, crop.rs:152-158: the output chunk; the others: input + output
+    const uint64_t per = zt::dtype_size(dtype_out) +
+                         (kind == ZT_PW_REENCODE ? 0 : zt::dtype_size(dtype_in));
+    *bytes = (uint64_t)numel(chunk_shape, ndim) * per;
+    return ZT_OK;
+}
+
+int zt_pointwise_apply_ndarray(zt_ctx* ctx, int dtype_in, const void* in, const int64_t* in_shape,
+                               int ndim, const int64_t* sub_start, const int64_t* sub_shape,
+                               const zt_pointwise_op* ops, int n_ops, void* out) {
+    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = check_shape(in_shape, ndim, "in_shape")) return rc;
+    zt::PwProgram prog;
+    if (int rc = build_pointwise_program(dtype_in, ops, n_ops, &prog)) return rc;
+    if ((sub_start == nullptr) != (sub_shape == nullptr))
+        return fail(ZT_ERR_INVALID_PARAMETERS, "sub_start and sub_shape go together");
+    int64_t start[ZT_MAX_DIMS], shape[ZT_MAX_DIMS], strides[ZT_MAX_DIMS];
+    for (int d = 0; d < ndim; ++d) {
+        start[d] = sub_start ? sub_start[d] : 0;
+        shape[d] = sub_shape ? sub_shape[d] : in_shape[d];
+        if (start[d] < 0 || shape[d] < 0 || start[d] + shape[d] > in_shape[d])
+            return fail(ZT_ERR_INVALID_PARAMETERS, "box outside the array on axis %d", d);
+    }
+    if (numel(shape, ndim) == 0) return ZT_OK;
+    if (!in || !out) return fail(ZT_ERR_INVALID_PARAMETERS, "null data pointer");
+    const int64_t isz = (int64_t)zt::dtype_size(dtype_in);
+    const int64_t osz = (int64_t)zt::dtype_size(prog.ops[n_ops - 1].dt_out);
+    if (((uintptr_t)in % isz) != 0 || ((uintptr_t)out % osz) != 0)
+        return fail(ZT_ERR_INVALID_PARAMETERS, "data pointers must be element aligned");
+    c_strides(in_shape, ndim, strides);
+    // Merge axis d into axis d-1 where the box spans axis d (the pair is then one axis of the
+    // source as well) and drop axes of extent 1: the whole contiguous array becomes one row.
+    zt::PwGeom g{};
+    int64_t ext[ZT_MAX_DIMS], str[ZT_MAX_DIMS];
+    int n = 0;
+    for (int d = 0; d < ndim; ++d) {
+        g.base += start[d] * strides[d];
+        if (shape[d] == 1) continue;
+        if (n > 0 && str[n - 1] == shape[d] * strides[d]) {  // axis d spanned: contiguous pair
+            ext[n - 1] *= shape[d];
+            str[n - 1] = strides[d];
+        } else {
+            ext[n] = shape[d];
+            str[n] = strides[d];
+            ++n;
+        }
+    }
+    // the row is the last axis when it has stride 1 (always, unless every extent was 1)
+    g.row_len = 1;
+    if (n > 0 && str[n - 1] == 1) g.row_len = ext[--n];
+    g.rows = 1;
+    g.n_outer = n;
+    for (int d = 0; d < n; ++d) {
+        g.shape[d] = ext[d];
+        g.stride[d] = str[d];
+        g.rows *= ext[d];
+    }
+    DeviceGuard guard(ctx->device);
+    if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev0, ctx->cur));
+    hipError_t e = zt::launch_pointwise(in, out, g, prog, ctx->cur);
+    if (e != hipSuccess) return hip_fail(e, "pointwise launch");
+    if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev1, ctx->cur));
+    return ZT_OK;
 }
 
 // ---- downsample ------------------------------------------------------------------------------

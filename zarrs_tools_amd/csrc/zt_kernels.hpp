@@ -163,6 +163,38 @@ constexpr int kSatTileW8 = 16;    // ... of 8 bytes
 hipError_t launch_sat_pass(const void* in, int dtype_in, void* out, int dtype_out, int64_t outer,
                            int64_t n, int64_t inner, const void* seed, void* last, hipStream_t s);
 
+// Pointwise programs (pointwise.hip; reencode.rs, crop.rs, rescale.rs, clamp.rs, equal.rs,
+// replace_value.rs): 1..kPwMaxOps ops on every element of a box. Op k reads the type op k-1
+// wrote (prog.dt_in for the first). Values are carried widened to a class (PwClass); the
+// immediates are class values' bits: clamp a / b = min / max `as` the op's input type; equal and
+// replace a = `value` in the input type; replace b = `replace` in the output type; rescale
+// a / b = the f64 bits of multiply / add.
+constexpr int kPwMaxOps = 8;
+enum PwKind : int { kPwCast = 0, kPwRescale = 1, kPwClamp = 2, kPwEqual = 3, kPwReplace = 4 };
+enum PwClass : int { kPwI32 = 0, kPwU32 = 1, kPwI64 = 2, kPwU64 = 3, kPwF32 = 4, kPwF64 = 5 };
+constexpr int kPwAddFirst = 1;  // rescale: (x + add) * multiply
+struct PwOp {
+    int32_t kind, dt_out, flags, pad;
+    uint64_t a, b;
+};
+struct PwProgram {
+    int32_t n_ops, dt_in;
+    PwOp ops[kPwMaxOps];
+};
+// The box as rows: `rows` rows of `row_len` contiguous source elements; row r starts at source
+// element base + sum_d idx_d * stride[d], idx = r unravelled over shape[0..n_outer) (C order);
+// the destination is contiguous. The launcher fills the fields below `stride`.
+struct PwGeom {
+    int64_t row_len, rows, base;
+    int32_t n_outer;
+    int64_t shape[kMaxDims - 1], stride[kMaxDims - 1];
+    int32_t log2_g, rows32;
+    int64_t segs, row_groups, step_rg, step_seg;
+};
+int pointwise_max_blocks();
+hipError_t launch_pointwise(const void* in, void* out, PwGeom g, const PwProgram& prog,
+                            hipStream_t s);
+
 // Synthetic inputs
 hipError_t launch_synth_step_noise_f32(float* out, int64_t n, int64_t plane, int64_t nx_row,
                                        int64_t nx_global, int64_t z0, uint64_t seed,

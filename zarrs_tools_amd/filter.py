@@ -12,6 +12,9 @@ Names, argument meaning and error behaviour follow LDeakin/zarrs_tools 0.7.2:
     memory_per_chunk :177, apply :197)
   - ``SummedAreaTable`` <- src/filter/filters/summed_area_table.rs (SummedAreaTable::new(
     chunk_limit), apply_dim :47, is_compatible :110, memory_per_chunk :136, apply :144)
+  - ``Reencode``, ``Crop``, ``Rescale``, ``Clamp``, ``Equal``, ``ReplaceValue`` <-
+    src/filter/filters/{reencode,crop,rescale,clamp,equal,replace_value}.rs (the per-element
+    filters; ``PointwiseProgram`` runs consecutive ones as one launch)
   - ``ArraySubsetOverlap`` <- src/filter/array_subset_overlap.rs:4-52
 Arrays are device-resident torch tensors (torch is used only for device memory and streams);
 every computation runs in libzarrs_tools_amd.so through the C ABI.
@@ -495,6 +498,316 @@ class SummedAreaTable:
             ctx.handle, DTYPES[input.dtype], _ptr(input.data.contiguous()),
             DTYPES[output.dtype], _ptr(output.data), i64_array(input.shape), len(input.shape),
             i64_array(output.chunk_shape)))
+
+
+def _invalid(msg: str):
+    return _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS, msg)
+
+
+_INT_BITS = {"int8": 8, "int16": 16, "int32": 32, "int64": 64,
+             "uint8": 8, "uint16": 16, "uint32": 32, "uint64": 64}
+
+
+def element_bits(value, dtype: str) -> int:
+    """A `value` / `replace` argument (the fill_value grammar of parse_fill_value: a JSON number,
+    true / false, "NaN", "Infinity", "-Infinity") as an element of `dtype`, the way
+    fill_value_from_metadata reads it: its storage bits, zero-extended (zt_pointwise_op's element
+    immediates). A value the type cannot hold (300 for uint8, 1.5 or "NaN" for an integer type,
+    a number for bool) raises InvalidParameters; the reference panics there. A float16 / bfloat16
+    value is rounded once from the f64, as half's from_f64 does (`f64 as f16` of the kernels)."""
+    import numpy as np
+    if dtype not in DTYPES:
+        raise _abi.UnsupportedDataType(_abi.ERR_UNSUPPORTED_DATA_TYPE,
+                                       f"Unsupported data type {dtype}")
+    bad = _invalid(f"value {value!r} is not compatible with data type {dtype}")
+    if dtype == "bool":
+        if not isinstance(value, bool):
+            raise bad
+        return int(value)
+    if isinstance(value, bool):
+        raise bad
+    if dtype in _INT_BITS:
+        if isinstance(value, float) and value.is_integer():
+            value = int(value)
+        if not isinstance(value, int):
+            raise bad
+        bits = _INT_BITS[dtype]
+        lo, hi = (-(1 << (bits - 1)), (1 << (bits - 1)) - 1) if dtype[0] == "i" else (
+            0, (1 << bits) - 1)
+        if not lo <= value <= hi:
+            raise bad
+        return value & ((1 << bits) - 1)
+    if isinstance(value, str):
+        if value not in ("NaN", "Infinity", "-Infinity"):
+            raise bad
+        x = {"NaN": math.nan, "Infinity": math.inf, "-Infinity": -math.inf}[value]
+    elif isinstance(value, (int, float)):
+        x = float(value)
+    else:
+        raise bad
+    if dtype == "float64":
+        return _f64_bits(x)
+    if dtype == "float32":
+        with np.errstate(all="ignore"):
+            return int(np.float32(x).view(np.uint32))
+    return _half_from_f64(x, dtype == "bfloat16")
+
+
+def _half_from_f64(x: float, bf16: bool) -> int:
+    """half 2.6.0's f16::from_f64 / bf16::from_f64 (f64_to_f16_bits / f64_to_bf16_bits of
+    csrc/zt_device.hpp, the kernel's `f64 as f16`): one rounding to nearest even, decided on the
+    upper 32 bits of the f64, never through f32."""
+    val = _f64_bits(x)
+    hi, lo = val >> 32, val & 0xFFFFFFFF
+    sign, exp, man = hi & 0x80000000, hi & 0x7FF00000, hi & 0x000FFFFF
+    ebits, mbits, bias = (8, 7, 127) if bf16 else (5, 10, 15)
+    shift = 20 - mbits  # mantissa bits of the upper word that are dropped
+    inf = ((1 << ebits) - 1) << mbits
+    if exp == 0x7FF00000:
+        nan_bit = 0 if (man == 0 and lo == 0) else 1 << (mbits - 1)
+        return (sign >> 16) | inf | nan_bit | (man >> shift)
+    half_sign = sign >> 16
+    half_exp = (exp >> 20) - 1023 + bias
+    if half_exp >= (1 << ebits) - 1:
+        return half_sign | inf
+    if half_exp <= 0:
+        if shift - half_exp > 21:
+            return half_sign
+        m = man | 0x00100000
+        half_man = m >> (shift + 1 - half_exp)
+        round_bit = 1 << (shift - half_exp)
+        if (m & round_bit) and (m & (3 * round_bit - 1)):
+            half_man += 1
+        return half_sign | half_man
+    r = half_sign | (half_exp << mbits) | (man >> shift)
+    round_bit = 1 << (shift - 1)
+    if (man & round_bit) and (man & (3 * round_bit - 1)):
+        r += 1
+    return r & 0xFFFF
+
+
+def _f64_bits(x: float) -> int:
+    import struct
+    return struct.unpack("<Q", struct.pack("<d", float(x)))[0]
+
+
+class _Pointwise:
+    """The operator surface the per-element filters share (FilterTraits, filter_traits.rs): `name`,
+    `is_compatible`, `memory_per_chunk`, `output_shape`, `output_data_type`, `apply_ndarray`,
+    `apply`; `op` is the filter as one zt_pointwise_op between two element types."""
+
+    kind = _abi.PW_REENCODE
+    _name = ""
+
+    def name(self) -> str:
+        return self._name
+
+    def is_compatible(self, dtype_in: str, dtype_out: str) -> None:
+        for d in (dtype_in, dtype_out):
+            if d not in DTYPES:
+                raise _abi.UnsupportedDataType(_abi.ERR_UNSUPPORTED_DATA_TYPE,
+                                               f"Unsupported data type {d}")
+        check(lib().zt_pointwise_is_compatible(self.kind, DTYPES[dtype_in], DTYPES[dtype_out]))
+
+    def memory_per_chunk(self, dtype_in: str, dtype_out: str, chunk_shape) -> int:
+        out = ctypes.c_uint64()
+        check(lib().zt_pointwise_memory_per_chunk(self.kind, DTYPES[dtype_in], DTYPES[dtype_out],
+                                                  i64_array(chunk_shape), len(chunk_shape),
+                                                  ctypes.byref(out)))
+        return int(out.value)
+
+    def output_shape(self, input_shape) -> tuple:
+        return tuple(int(s) for s in input_shape)
+
+    def output_data_type(self, dtype_in: str):
+        """(data type, fill value) when the filter sets the output type itself, else None."""
+        return None
+
+    def crop_box(self, input_shape):
+        """(offset, shape) of the input box the output reads, None for the whole array."""
+        return None
+
+    def _imm(self, dtype_in: str, dtype_out: str):
+        return 0, 0, 0
+
+    def op(self, dtype_in: str, dtype_out: str) -> "_abi.PointwiseOp":
+        self.is_compatible(dtype_in, dtype_out)
+        imm0, imm1, flags = self._imm(dtype_in, dtype_out)
+        return _abi.PointwiseOp(self.kind, DTYPES[dtype_out], imm0, imm1, flags, 0)
+
+    def apply_ndarray(self, v, dtype_out: Optional[str] = None, ctx: Optional[Context] = None):
+        """The filter's element work on a device block (the box of `crop_box` for a crop);
+        returns a new tensor of `dtype_out` (default: the filter's own output type, else the
+        input's)."""
+        dtype_in = dtype_of(v)
+        auto = self.output_data_type(dtype_in)
+        dtype_out = dtype_out or (auto[0] if auto else dtype_in)
+        return PointwiseProgram([self], dtype_in, [dtype_out], v.shape).apply_ndarray(v, ctx)
+
+    def apply(self, input: DeviceArray, output: DeviceArray,
+              ctx: Optional[Context] = None) -> None:
+        """The filter's `apply` over a device-resident array: one launch."""
+        PointwiseProgram([self], input.dtype, [output.dtype], input.shape).run(
+            input.data, output.data, ctx)
+
+
+class Reencode(_Pointwise):
+    """reencode.rs:35-219 — `Reencode::new(chunk_limit)`: every element `as` the output type."""
+    _name = "reencode"
+
+    def __init__(self, chunk_limit: Optional[int] = None):
+        self.chunk_limit = chunk_limit
+
+
+class Crop(_Pointwise):
+    """crop.rs:46-248 — `Crop::new(offset, shape, chunk_limit)`: output element i is input
+    element offset + i, `as` the output type; the output has `shape`."""
+    _name = "crop"
+
+    def __init__(self, offset: Sequence[int], shape: Sequence[int],
+                 chunk_limit: Optional[int] = None):
+        self.offset = tuple(int(o) for o in offset)
+        self.shape = tuple(int(s) for s in shape)
+        if any(o < 0 for o in self.offset) or any(s < 0 for s in self.shape):
+            raise _invalid("crop offset and shape are unsigned")
+        self.chunk_limit = chunk_limit
+
+    def crop_box(self, input_shape):
+        nd = len(input_shape)
+        if len(self.offset) != nd or len(self.shape) != nd:
+            raise _invalid(f"crop offset and shape need one entry per axis ({nd})")
+        for o, s, n in zip(self.offset, self.shape, input_shape):
+            if o + s > n:
+                raise _invalid(f"crop offset {list(self.offset)} + shape {list(self.shape)} "
+                               f"is beyond the input {list(input_shape)}")
+        return self.offset, self.shape
+
+    def output_shape(self, input_shape) -> tuple:
+        """Crop::output_shape (crop.rs:160-162)."""
+        return self.crop_box(input_shape)[1]
+
+
+class Rescale(_Pointwise):
+    """rescale.rs:51-240 — `Rescale::new(multiply, add, add_first, chunk_limit)`: in f64,
+    fma(v, multiply, add) (one rounding), or (v + add) * multiply with add_first."""
+    kind = _abi.PW_RESCALE
+    _name = "rescale"
+
+    def __init__(self, multiply: float, add: float, add_first: bool = False,
+                 chunk_limit: Optional[int] = None):
+        self.multiply, self.add, self.add_first = float(multiply), float(add), bool(add_first)
+        self.chunk_limit = chunk_limit
+
+    def _imm(self, dtype_in, dtype_out):
+        return (_f64_bits(self.multiply), _f64_bits(self.add),
+                _abi.PW_ADD_FIRST if self.add_first else 0)
+
+
+class Clamp(_Pointwise):
+    """clamp.rs:44-212 — `Clamp::new(min, max, chunk_limit)`: num_traits::clamp between
+    `min as TIn` and `max as TIn`, then `as` the output type."""
+    kind = _abi.PW_CLAMP
+    _name = "clamp"
+
+    def __init__(self, min: float, max: float, chunk_limit: Optional[int] = None):
+        self.min, self.max = float(min), float(max)
+        self.chunk_limit = chunk_limit
+
+    def _imm(self, dtype_in, dtype_out):
+        return _f64_bits(self.min), _f64_bits(self.max), 0
+
+
+class Equal(_Pointwise):
+    """equal.rs:52-215 — `Equal::new(value, chunk_limit)`: (v == value) as bool or uint8; a NaN
+    `value` equals nothing."""
+    kind = _abi.PW_EQUAL
+    _name = "equal"
+
+    def __init__(self, value, chunk_limit: Optional[int] = None):
+        self.value = value
+        self.chunk_limit = chunk_limit
+
+    def output_data_type(self, dtype_in: str):
+        """Equal::output_data_type (equal.rs:121-123): bool with fill value false."""
+        return "bool", False
+
+    def _imm(self, dtype_in, dtype_out):
+        return element_bits(self.value, dtype_in), 0, 0
+
+
+class ReplaceValue(_Pointwise):
+    """replace_value.rs:63-241 — `ReplaceValue::new(value, replace, chunk_limit)`:
+    v == value ? replace : v as the output type (`value` in the input type, `replace` in the
+    output type); a NaN `value` replaces nothing."""
+    kind = _abi.PW_REPLACE_VALUE
+    _name = "replace_value"
+
+    def __init__(self, value, replace, chunk_limit: Optional[int] = None):
+        self.value, self.replace = value, replace
+        self.chunk_limit = chunk_limit
+
+    def _imm(self, dtype_in, dtype_out):
+        return element_bits(self.value, dtype_in), element_bits(self.replace, dtype_out), 0
+
+
+POINTWISE = {"reencode": Reencode, "crop": Crop, "rescale": Rescale, "clamp": Clamp,
+             "equal": Equal, "replace_value": ReplaceValue}
+
+
+class PointwiseProgram:
+    """Consecutive per-element filters as one launch (zt_pointwise_apply_ndarray): filter k reads
+    the type filter k-1 wrote (`dtype_in` for the first) and writes dtypes_out[k]; crops compose
+    by adding their offsets, since per-element ops commute with the selection. At most
+    PW_MAX_OPS (8) filters."""
+
+    def __init__(self, filters: Sequence[_Pointwise], dtype_in: str, dtypes_out: Sequence[str],
+                 input_shape: Sequence[int]):
+        if not 1 <= len(filters) <= _abi.PW_MAX_OPS or len(filters) != len(dtypes_out):
+            raise _invalid(f"a pointwise program has 1 to {_abi.PW_MAX_OPS} filters, each with "
+                           "its output type")
+        self.dtype_in = dtype_in
+        self.dtype_out = dtypes_out[-1]
+        self.input_shape = tuple(int(s) for s in input_shape)
+        nd = len(self.input_shape)
+        self.offset, self.shape = (0,) * nd, self.input_shape
+        self.cropped = False
+        ops, dt = [], dtype_in
+        for f, dout in zip(filters, dtypes_out):
+            box = f.crop_box(self.shape)
+            if box is not None:
+                self.offset = tuple(a + b for a, b in zip(self.offset, box[0]))
+                self.shape = tuple(box[1])
+                self.cropped = True
+            ops.append(f.op(dt, dout))
+            dt = dout
+        self.ops = (_abi.PointwiseOp * len(ops))(*ops)
+        self.n_ops = len(ops)
+
+    def box(self):
+        """(offset, shape) i64 arrays of the composed crop, or (None, None)."""
+        if not self.cropped:
+            return None, None
+        return i64_array(self.offset), i64_array(self.shape)
+
+    def run(self, x, y, ctx: Optional[Context] = None) -> None:
+        """x (device tensor, input_shape, dtype_in) -> y (contiguous, the box's shape,
+        dtype_out)."""
+        if tuple(x.shape) != self.input_shape or tuple(y.shape) != tuple(self.shape):
+            raise _invalid("pointwise program: array shapes differ from the program's")
+        if not y.is_contiguous():
+            raise _invalid("pointwise program: the output must be contiguous")
+        x = x.contiguous()
+        ctx = ctx or default_context(x.device.index)
+        off, shp = self.box()
+        check(lib().zt_pointwise_apply_ndarray(
+            ctx.handle, DTYPES[self.dtype_in], _ptr(x), i64_array(self.input_shape),
+            len(self.input_shape), off, shp, self.ops, self.n_ops, _ptr(y)))
+
+    def apply_ndarray(self, v, ctx: Optional[Context] = None):
+        torch = _torch()
+        out = torch.empty(tuple(self.shape), dtype=torch_dtype(self.dtype_out), device=v.device)
+        self.run(v, out, ctx)
+        return out
 
 
 class Downsample:

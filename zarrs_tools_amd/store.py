@@ -355,6 +355,112 @@ def summed_area_table(input_path, output_path, data_type: Optional[str] = None, 
     return st.as_dict()
 
 
+def pointwise_output(filt, input_data_type: str, data_type: Optional[str] = None, encoding=None):
+    """(output data type, encoding) of a per-element filter's output array, as
+    output_array_builder decides it (filter_traits.rs:47-82): an explicit data type (`data_type`
+    or the encoding's) wins; else the filter's own (Equal::output_data_type: bool with fill value
+    false, equal.rs:121-123), which also sets the fill value; else the input's."""
+    enc = dict(encoding) if isinstance(encoding, dict) else (
+        json.loads(encoding) if encoding else {})
+    dt = enc.get("data_type") or data_type
+    if dt is None:
+        auto = filt.output_data_type(input_data_type)
+        if auto is not None:
+            dt, enc["fill_value"] = auto
+    if dt is not None:
+        enc["data_type"] = dt
+    return dt or input_data_type, (enc or None)
+
+
+def pointwise(input_path, output_path, filters, dtypes_out, device: int = 0, rows=None,
+              nthreads: int = 0, erase: bool = True, finish: bool = True, encoding=None,
+              chunk_limit: int = 0) -> dict:
+    """Consecutive per-element filters (filter.Reencode ... ReplaceValue) over a store in one
+    pass (zt_store_pointwise): filter k writes dtypes_out[k]; the last one is the output array's
+    data type and must agree with `encoding`."""
+    from .filter import PointwiseProgram
+    info = open_array(input_path)
+    prog = PointwiseProgram(filters, info.data_type, dtypes_out, info.shape)
+    off, shp = prog.box()
+    set_chunk_limit(chunk_limit)
+    st = _abi.StoreStats()
+    r0, r1 = (0, -1) if rows is None else (int(rows[0]), int(rows[1]))
+    check(lib().zt_store_pointwise(_b(input_path), _b(output_path), _dt(dtypes_out[-1]),
+                                   _enc(encoding), prog.ops, prog.n_ops, off, shp, int(device),
+                                   r0, r1, int(nthreads), _flags(erase, finish),
+                                   ctypes.byref(st)))
+    return st.as_dict()
+
+
+def _pointwise_one(filt, input_path, output_path, data_type, encoding, **kw) -> dict:
+    dt, enc = pointwise_output(filt, open_array(input_path).data_type, data_type, encoding)
+    return pointwise(input_path, output_path, [filt], [dt], encoding=enc, **kw)
+
+
+def reencode(input_path, output_path, data_type: Optional[str] = None, device: int = 0,
+             rows=None, nthreads: int = 0, erase: bool = True, finish: bool = True,
+             encoding=None, chunk_limit: int = 0) -> dict:
+    """zarrs_filter reencode INPUT OUTPUT [--data-type T ...] (reencode.rs:128-218)."""
+    from .filter import Reencode
+    return _pointwise_one(Reencode(), input_path, output_path, data_type, encoding,
+                          device=device, rows=rows, nthreads=nthreads, erase=erase,
+                          finish=finish, chunk_limit=chunk_limit)
+
+
+def crop(input_path, output_path, offset, shape, data_type: Optional[str] = None,
+         device: int = 0, rows=None, nthreads: int = 0, erase: bool = True, finish: bool = True,
+         encoding=None, chunk_limit: int = 0) -> dict:
+    """zarrs_filter crop INPUT OUTPUT OFFSET SHAPE [--data-type T] (crop.rs:164-247)."""
+    from .filter import Crop
+    return _pointwise_one(Crop(offset, shape), input_path, output_path, data_type, encoding,
+                          device=device, rows=rows, nthreads=nthreads, erase=erase,
+                          finish=finish, chunk_limit=chunk_limit)
+
+
+def rescale(input_path, output_path, multiply: float, add: float, add_first: bool = False,
+            data_type: Optional[str] = None, device: int = 0, rows=None, nthreads: int = 0,
+            erase: bool = True, finish: bool = True, encoding=None,
+            chunk_limit: int = 0) -> dict:
+    """zarrs_filter rescale INPUT OUTPUT MULTIPLY ADD [--add-first] [--data-type T]
+    (rescale.rs:160-239)."""
+    from .filter import Rescale
+    return _pointwise_one(Rescale(multiply, add, add_first), input_path, output_path, data_type,
+                          encoding, device=device, rows=rows, nthreads=nthreads, erase=erase,
+                          finish=finish, chunk_limit=chunk_limit)
+
+
+def clamp(input_path, output_path, min: float, max: float, data_type: Optional[str] = None,
+          device: int = 0, rows=None, nthreads: int = 0, erase: bool = True, finish: bool = True,
+          encoding=None, chunk_limit: int = 0) -> dict:
+    """zarrs_filter clamp INPUT OUTPUT MIN MAX [--data-type T] (clamp.rs:108-211)."""
+    from .filter import Clamp
+    return _pointwise_one(Clamp(min, max), input_path, output_path, data_type, encoding,
+                          device=device, rows=rows, nthreads=nthreads, erase=erase,
+                          finish=finish, chunk_limit=chunk_limit)
+
+
+def equal(input_path, output_path, value, data_type: Optional[str] = None, device: int = 0,
+          rows=None, nthreads: int = 0, erase: bool = True, finish: bool = True, encoding=None,
+          chunk_limit: int = 0) -> dict:
+    """zarrs_filter equal INPUT OUTPUT VALUE [--data-type bool|uint8] (equal.rs:125-214); the
+    output is bool with fill value false unless a data type is given."""
+    from .filter import Equal
+    return _pointwise_one(Equal(value), input_path, output_path, data_type, encoding,
+                          device=device, rows=rows, nthreads=nthreads, erase=erase,
+                          finish=finish, chunk_limit=chunk_limit)
+
+
+def replace_value(input_path, output_path, value, replace, data_type: Optional[str] = None,
+                  device: int = 0, rows=None, nthreads: int = 0, erase: bool = True,
+                  finish: bool = True, encoding=None, chunk_limit: int = 0) -> dict:
+    """zarrs_filter replace-value INPUT OUTPUT VALUE REPLACE [--data-type T]
+    (replace_value.rs:135-240)."""
+    from .filter import ReplaceValue
+    return _pointwise_one(ReplaceValue(value, replace), input_path, output_path, data_type,
+                          encoding, device=device, rows=rows, nthreads=nthreads, erase=erase,
+                          finish=finish, chunk_limit=chunk_limit)
+
+
 def downsample_gaussian(input_path, output_path, stride, sigma, kernel_half_size,
                         data_type: Optional[str] = None, device: int = 0, rows=None,
                         nthreads: int = 0, erase: bool = True, finish: bool = True,

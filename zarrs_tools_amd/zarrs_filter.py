@@ -1,4 +1,6 @@
-"""``zarrs_filter`` for the on-path filters: guided_filter and downsample over Zarr V3 stores.
+"""``zarrs_filter`` for the on-path filters (guided_filter, downsample, gaussian,
+summed_area_table and the per-element reencode, crop, rescale, clamp, equal, replace_value) over
+Zarr V3 stores.
 
 Mirrors src/bin/zarrs_filter.rs (LDeakin/zarrs_tools 0.7.2) for the filters this framework
 accelerates:
@@ -7,21 +9,35 @@ accelerates:
         [--device D] [RUN_CONFIG.json] [guided-filter IN OUT EPSILON RADIUS [--data-type T]
                                         | downsample IN OUT STRIDE [--discrete] [--data-type T]
                                         | gaussian IN OUT SIGMA KERNEL_HALF_SIZE [--data-type T]
-                                        | summed-area-table IN OUT [--data-type T]]
+                                        | summed-area-table IN OUT [--data-type T]
+                                        | reencode IN OUT | crop IN OUT OFFSET SHAPE
+                                        | rescale IN OUT MULTIPLY ADD [--add-first]
+                                        | clamp IN OUT MIN MAX | equal IN OUT VALUE
+                                        | replace-value IN OUT VALUE REPLACE]
 
 * subcommand arguments as GuidedFilterArguments (guided_filter.rs:25-33),
   DownsampleArguments (downsample.rs:20-33, STRIDE comma delimited) and GaussianArguments
   (gaussian.rs:22-30, SIGMA and KERNEL_HALF_SIZE comma delimited, one entry per axis);
   summed-area-table takes none of its own (SummedAreaTableArguments, summed_area_table.rs:22-23);
+  the per-element filters as ReencodeArguments (reencode.rs:20), CropArguments (crop.rs:20-27,
+  OFFSET and SHAPE comma delimited), RescaleArguments (rescale.rs:20-31), ClampArguments
+  (clamp.rs:20-25), EqualArguments (equal.rs:23-34) and ReplaceValueArguments
+  (replace_value.rs:23-44); VALUE and REPLACE follow parse_fill_value (a JSON number, true /
+  false, NaN, Infinity, -Infinity) and negative numbers parse as values;
 * a JSON run config is a list of {"filter": "guided_filter" | "downsample" | "gaussian" |
-  "summed_area_table", "input", "output",
-  ...args, "data_type"}, with "$name" meaning a named temporary array under --tmp and an omitted
-  input meaning the previous filter's output (zarrs_filter.rs:106-138, :338-381);
+  "summed_area_table" | "reencode" | "crop" | "rescale" | "clamp" | "equal" | "replace_value",
+  "input", "output", ...args (offset, shape, multiply, add, add_first, min, max, value, replace
+  for the per-element filters), "data_type"}, with "$name" meaning a named temporary array
+  under --tmp and an omitted input meaning the previous filter's output (zarrs_filter.rs:106-138,
+  :338-381);
 * a chain of steps linked only through temporaries (a "$name" or implicit output read by the
   next step alone) runs device-resident when its arrays fit 80 % of the free device memory: the
   chain input is read once, every step runs on the arrays in HBM, the last output is written
   once; the temporaries' zarr.json are created as the store path would create them, but their
-  chunks never go through the store (`--no-device-chain` forces the store path);
+  chunks never go through the store (`--no-device-chain` forces the store path); inside such a
+  chain a run of consecutive per-element steps is one kernel launch that reads each element once
+  and writes it once (up to 8 steps per launch; crops compose by adding their offsets;
+  `--no-pointwise-fusion` launches them one by one);
 * every filter takes the reencoding arguments (ZarrReencodingArgs, lib.rs:274-377: -d/--data-type,
   -f/--fill-value, --separator, -c/--chunk-shape, -s/--shard-shape, --array-to-array-codecs,
   --array-to-bytes-codec, --bytes-to-bytes-codecs, --dimension-names, --attributes,
@@ -33,21 +49,22 @@ accelerates:
   `step/steps rw:READ/WRITE p:PROCESS` (thread-seconds, device seconds), like zarrs_filter.rs:
   149-172.
 
-Filters outside the accelerated path (reencode, crop, rescale, clamp, equal, replace_value,
-gradient_magnitude) are rejected with FilterError::Other: they are out of scope (DESIGN.md §1;
-gradient_magnitude runs from the library only). A summed-area table's chunk rows each need the
-previous row's last plane, so with --gpus > 1 that step runs in one process on the first device
-(`rows_splittable`). `--chunk-limit N` bounds the chunks in flight (decoded input rows + output rows
-being computed or encoded, and the host worker threads) at N, down to the pipeline's unit of one
-slab and one output row (guided_filter.rs:251-258); independently the rows held in memory are
-bounded by 80 % of the available host and device memory, failing like calculate_chunk_limit
-(filter.rs:52-66) when not even one row fits.
+gradient_magnitude is rejected with FilterError::Other: it runs from the library only
+(DESIGN.md §1). A summed-area table's chunk rows each need the previous row's last plane, so with
+--gpus > 1 that step runs in one process on the first device (`rows_splittable`); the other
+filters' rows, the per-element ones included, are split over the processes. `--chunk-limit N`
+bounds the chunks in flight (decoded input rows + output rows being computed or encoded, and the
+host worker threads) at N, down to the pipeline's unit of one slab and one output row
+(guided_filter.rs:251-258); independently the rows held in memory are bounded by 80 % of the
+available host and device memory, failing like calculate_chunk_limit (filter.rs:52-66) when not
+even one row fits.
 """
 from __future__ import annotations
 
 import argparse
 import json
 import os
+import re
 import shutil
 import sys
 import tempfile
@@ -58,7 +75,8 @@ import numpy as np
 from . import _abi
 from . import store as S
 
-ON_PATH = ("guided_filter", "downsample", "gaussian", "summed_area_table")
+POINTWISE = ("reencode", "crop", "rescale", "clamp", "equal", "replace_value")
+ON_PATH = ("guided_filter", "downsample", "gaussian", "summed_area_table") + POINTWISE
 
 
 def rows_splittable(name: str) -> bool:
@@ -142,6 +160,9 @@ def build_parser() -> argparse.ArgumentParser:
                          "output chunk rows")
     ap.add_argument("--no-device-chain", action="store_true",
                     help="run every step store -> store, also chains of temporaries")
+    ap.add_argument("--no-pointwise-fusion", action="store_true",
+                    help="in a device-resident chain, launch consecutive per-element steps one "
+                         "by one")
     sub = ap.add_subparsers(dest="filter")
     g = sub.add_parser("guided-filter", help="Apply a guided filter (edge preserving noise filter).")
     g.add_argument("input")
@@ -165,6 +186,44 @@ def build_parser() -> argparse.ArgumentParser:
     sa.add_argument("input")
     sa.add_argument("output")
     _add_reencode_args(sa)
+    # the per-element filters; their numbers may be negative (-1e-3 included) and VALUE may be
+    # -Infinity, which argparse would otherwise take for options. This sets argparse's
+    # `_negative_number_matcher`, an undocumented attribute of ArgumentParser (CPython 3.2 to
+    # 3.13 consult it in `_parse_optional`): an argument that matches it is a positional as long
+    # as the parser has no option that looks like a negative number. tests/test_pointwise.py
+    # (test_subcommand_grammar_of_the_six) fails if a Python version stops honouring it.
+    number = re.compile(r"^-(\d+\.?\d*|\d*\.\d+)([eE][-+]?\d+)?$|^-Infinity$")
+
+    def pointwise(name, help):
+        p = sub.add_parser(name, help=help)
+        p._negative_number_matcher = number
+        p.add_argument("input")
+        p.add_argument("output")
+        return p
+
+    re_ = pointwise("reencode", "Reencode an array.")
+    _add_reencode_args(re_)
+    cr = pointwise("crop", "Crop an array given an offset and shape.")
+    cr.add_argument("offset", type=_parse_stride)
+    cr.add_argument("shape", type=_parse_stride)
+    _add_reencode_args(cr)
+    rs = pointwise("rescale", "Rescale array values given a multiplier and offset.")
+    rs.add_argument("multiply", type=float)
+    rs.add_argument("add", type=float)
+    rs.add_argument("--add-first", action="store_true",
+                    help="perform the addition before the multiplication")
+    _add_reencode_args(rs)
+    cl = pointwise("clamp", "Clamp values between a minimum and maximum.")
+    cl.add_argument("min", type=float)
+    cl.add_argument("max", type=float)
+    _add_reencode_args(cl)
+    eq = pointwise("equal", "Return a binary image where the input is equal to some value.")
+    eq.add_argument("value", type=_parse_fill_value)
+    _add_reencode_args(eq)
+    rv = pointwise("replace-value", "Replace a value with another value.")
+    rv.add_argument("value", type=_parse_fill_value)
+    rv.add_argument("replace", type=_parse_fill_value)
+    _add_reencode_args(rv)
     return ap
 
 
@@ -185,6 +244,13 @@ def _steps_from_cli(a) -> list:
         return [{"filter": "summed_area_table", "input": a.input, "output": a.output,
                  "data_type": a.data_type, "chunk_limit": a.filter_chunk_limit,
                  **_reencode_of(a)}]
+    own = {"reencode": (), "crop": ("offset", "shape"),
+           "rescale": ("multiply", "add", "add_first"), "clamp": ("min", "max"),
+           "equal": ("value",), "replace-value": ("value", "replace")}
+    if a.filter in own:
+        return [{"filter": a.filter.replace("-", "_"), "input": a.input, "output": a.output,
+                 **{k: getattr(a, k) for k in own[a.filter]}, "data_type": a.data_type,
+                 "chunk_limit": a.filter_chunk_limit, **_reencode_of(a)}]
     return []
 
 
@@ -222,10 +288,63 @@ def plan_chains(steps: list) -> list:
     return chains
 
 
+def pointwise_filter(step: dict):
+    """The per-element filter object of a run-config step (keys as the reference's *Arguments
+    structs: offset, shape; multiply, add, add_first; min, max; value; value, replace)."""
+    from . import filter as F
+    name = step.get("filter")
+
+    def need(*keys):
+        missing = [k for k in keys if step.get(k) is None]
+        if missing:
+            raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS,
+                                         f"{name} needs {', '.join(missing)}")
+        return [step[k] for k in keys]
+
+    def ints(v):
+        return _parse_stride(v) if isinstance(v, str) else [int(x) for x in v]
+
+    if name == "reencode":
+        return F.Reencode()
+    if name == "crop":
+        offset, shape = need("offset", "shape")
+        return F.Crop(ints(offset), ints(shape))
+    if name == "rescale":
+        multiply, add = need("multiply", "add")
+        return F.Rescale(float(multiply), float(add), bool(step.get("add_first", False)))
+    if name == "clamp":
+        lo, hi = need("min", "max")
+        return F.Clamp(float(lo), float(hi))
+    if name == "equal":
+        return F.Equal(need("value")[0])
+    if name == "replace_value":
+        value, replace = need("value", "replace")
+        return F.ReplaceValue(value, replace)
+    raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS, f"{name} is not a per-element filter")
+
+
+def step_encoding(step: dict, in_data_type: str):
+    """The reencoding a step's output array is created with: encoding_of(step), and for a
+    per-element filter that sets its own output type (equal: bool, fill value false) that type
+    when the step gives none (output_array_builder, filter_traits.rs:47-82)."""
+    enc = encoding_of(step)
+    if step.get("filter") in POINTWISE:
+        _dt, enc = S.pointwise_output(pointwise_filter(step), in_data_type,
+                                      step.get("data_type"), enc)
+    return enc
+
+
 def _step_params(step, info):
     """(filter object, output shape, output data type) of a run-config step on an input array."""
     from . import filter as F
     name = step.get("filter")
+    if name in POINTWISE:
+        f = pointwise_filter(step)
+        dt, _enc = S.pointwise_output(f, info.data_type, step.get("data_type"),
+                                      encoding_of(step))
+        f.is_compatible(info.data_type, dt)
+        f.op(info.data_type, dt)  # value / replace must fit the types
+        return f, f.output_shape(info.shape), dt
     dt = step.get("data_type") or (encoding_of(step) or {}).get("data_type") or info.data_type
     if name == "guided_filter":
         if "epsilon" not in step or "radius" not in step:
@@ -401,24 +520,46 @@ def write_from_device(path, x, nthreads: int = 0, start=None) -> None:
                 f.result()
 
 
+def plan_pointwise_fusion(names: list, fuse: bool = True, max_ops: int = 8) -> list:
+    """The launches of a device-resident chain: [(i, j)] covering every step in order, (i, j)
+    with j > i a maximal run of consecutive per-element steps (at most `max_ops`, a longer run is
+    split) that becomes one kernel launch; every other step, and every step with fuse=False, is
+    its own (i, i)."""
+    groups, i = [], 0
+    while i < len(names):
+        j = i
+        if fuse and names[i] in POINTWISE:
+            while j + 1 < len(names) and names[j + 1] in POINTWISE and j + 1 - i < max_ops:
+                j += 1
+        groups.append((i, j))
+        i = j + 1
+    return groups
+
+
 def run_device_chain(steps: list, paths: list, device: int = 0, nthreads: int = 0,
-                     log=print, budget_frac: float = 0.8):
+                     log=print, budget_frac: float = 0.8, fuse_pointwise: bool = True):
     """Run steps[0..] device-resident: paths[k] is step k's input path (paths[k+1] its output).
     Creates every output array as the store path would (S.create_output), reads paths[0] once,
-    applies the filters on HBM arrays, writes the last output once. Returns per-step stats, or
+    applies the filters on HBM arrays, writes the last output once. A run of consecutive
+    per-element steps (plan_pointwise_fusion) is one launch whose intermediates are never
+    materialised; their zarr.json are created all the same. Returns per-step stats (a
+    fused-away step reports kernel_s 0 and `fused_into`, the step that carries the launch), or
     None (nothing done) when the chain's arrays do not fit `budget_frac` of the free device
     memory, in which case the caller runs it store -> store."""
     import torch
     from . import filter as F
     # shapes / types of every array of the chain (metadata only)
     plan, info = [], S.open_array(paths[0])
-    peak = 0
     for k, step in enumerate(steps):
         f, oshape, odt = _step_params(step, info)
-        peak = max(peak, _nbytes(info.shape, info.data_type) + _nbytes(oshape, odt))
         plan.append((f, info, oshape, odt))
         info = S.ArrayInfo(paths[k + 1], odt, tuple(oshape), info.chunk_shape,
                            info.inner_chunk_shape)
+    groups = plan_pointwise_fusion([st.get("filter") for st in steps], fuse_pointwise,
+                                   _abi.PW_MAX_OPS)
+    # only the arrays that are materialised count: each launch's input and output
+    peak = max(_nbytes(plan[i][1].shape, plan[i][1].data_type) + _nbytes(plan[j][2], plan[j][3])
+               for i, j in groups)
     free, _total = torch.cuda.mem_get_info(device)
     if 2 * peak > budget_frac * free:  # in + out of a step, plus filter scratch of the same order
         return None
@@ -439,7 +580,8 @@ def run_device_chain(steps: list, paths: list, device: int = 0, nthreads: int = 
     t_read = time.perf_counter() - t0
     for k, step in enumerate(steps):
         f, src_info_k, oshape, odt = plan[k]
-        S.create_output(paths[k], paths[k + 1], odt, oshape, encoding_of(step))
+        S.create_output(paths[k], paths[k + 1], odt, oshape,
+                        step_encoding(step, src_info_k.data_type))
     # The last output is "not finished" (no zarr.json, zarrs_filter.rs:297-313) until its chunks
     # are written; a failing step leaves no output that looks complete. Held only once the input
     # is on the device, so a fallback to the store path never leaves a stale pending file.
@@ -447,21 +589,33 @@ def run_device_chain(steps: list, paths: list, device: int = 0, nthreads: int = 
     dev = torch.device("cuda", device)
     x_dt, x_chunk = src_info.data_type, src_info.chunk_shape
     ctx = F.default_context(device)
-    for k, step in enumerate(steps):
-        f = plan[k][0]
-        out_info = S.open_array(paths[k + 1])
+    for i, j in groups:
+        out_info = S.open_array(paths[j + 1])
         y = torch.empty(tuple(out_info.shape), dtype=F.torch_dtype(out_info.data_type), device=dev)
+        names = "+".join(str(steps[k].get("filter")) for k in range(i, j + 1))
         t1 = time.perf_counter()
-        f.apply(F.DeviceArray(x, x_chunk, x_dt), F.DeviceArray(y, out_info.chunk_shape,
-                                                              out_info.data_type), ctx=ctx)
+        if j > i:
+            prog = F.PointwiseProgram([plan[k][0] for k in range(i, j + 1)], x_dt,
+                                      [plan[k][3] for k in range(i, j + 1)], x.shape)
+            prog.run(x, y, ctx)
+        else:
+            plan[i][0].apply(F.DeviceArray(x, x_chunk, x_dt),
+                             F.DeviceArray(y, out_info.chunk_shape, out_info.data_type), ctx=ctx)
         ctx.synchronize()
         t_k = time.perf_counter() - t1
-        log(f"{k}: {step.get('filter')} device-resident {list(x.shape)} {x_dt} -> "
+        log(f"{i if j == i else f'{i}-{j}'}: {names} device-resident {list(x.shape)} {x_dt} -> "
             f"{list(y.shape)} {out_info.data_type} in {t_k:.3f}s")
-        results.append({"wall_s": t_k, "decode_s": t_read if k == 0 else 0.0, "encode_s": 0.0,
-                        "h2d_s": 0.0, "kernel_s": t_k, "d2h_s": 0.0, "bytes_read": 0,
-                        "bytes_written": 0, "voxels": int(y.numel()), "rows": 0,
-                        "threads": nthreads, "device_resident": True})
+        for k in range(i, j + 1):
+            carrier = k == j
+            st = {"wall_s": t_k if carrier else 0.0, "decode_s": t_read if k == 0 else 0.0,
+                  "encode_s": 0.0, "h2d_s": 0.0, "kernel_s": t_k if carrier else 0.0,
+                  "d2h_s": 0.0, "bytes_read": 0, "bytes_written": 0,
+                  "voxels": int(y.numel()) if carrier else 0, "rows": 0, "threads": nthreads,
+                  "device_resident": True}
+            if j > i:
+                st["fused_into" if not carrier else "fused_steps"] = (
+                    j if not carrier else list(range(i, j + 1)))
+            results.append(st)
         x, x_dt, x_chunk = y, out_info.data_type, out_info.chunk_shape
     t2 = time.perf_counter()
     write_from_device(paths[-1], x, nthreads)
@@ -486,10 +640,22 @@ def _rows_worker(name: str, src: str, dst: str, params: dict, device: int, rows,
         return S.guided_filter(src, dst, params["epsilon"], params["radius"], cols=cols, **kw)
     if name == "gaussian":
         return S.gaussian(src, dst, params["sigma"], params["kernel_half_size"], **kw)
+    if name in POINTWISE:
+        return _store_pointwise(name, src, dst, params["args"], **kw)
     if name == "downsample_gaussian":  # a zarrs_ome level with --gaussian-sigma
         return S.downsample_gaussian(src, dst, params["stride"], params["sigma"],
                                      params["kernel_half_size"], **kw)
+    if name != "downsample":
+        raise _abi.FilterError(_abi.ERR_OTHER, f"no store step for filter {name!r}")
     return S.downsample(src, dst, params["stride"], discrete=params["discrete"], **kw)
+
+
+def _store_pointwise(name: str, src: str, dst: str, args: dict, **kw) -> dict:
+    """A per-element step store -> store: `args` holds the filter's own run-config keys."""
+    f = pointwise_filter({"filter": name, **args})
+    dt, enc = S.pointwise_output(f, S.open_array(src).data_type, kw.pop("data_type", None),
+                                 kw.pop("encoding", None))
+    return S.pointwise(src, dst, [f], [dt], encoding=enc, **kw)
 
 
 def run_rows_parallel(name: str, src: str, dst: str, params: dict, out_shape, gpus: int,
@@ -566,10 +732,13 @@ def _device_ok(device: int) -> bool:
 
 def run(steps: list, exists: str = "erase", tmp: str | None = None,
         chunk_limit: int | None = None, device: int = 0, stats: bool = False,
-        log=print, device_chain: bool = True, gpus: int = 1, gpu_devices=None) -> list:
+        log=print, device_chain: bool = True, gpus: int = 1, gpu_devices=None,
+        fuse_pointwise: bool = True) -> list:
     """Run a list of filter steps (the run-config form); returns the per-step stats. gpus > 1:
     every store step is split over that many processes by output chunk rows (one per GPU;
-    `gpu_devices` maps process g to a device, default g); device-resident chains are then off."""
+    `gpu_devices` maps process g to a device, default g); device-resident chains are then off.
+    fuse_pointwise=False launches the per-element steps of a device-resident chain one by one
+    (the same results, more passes over HBM)."""
     if gpus > 1:
         device_chain = False
     tmp_root = tmp or tempfile.gettempdir()
@@ -621,6 +790,13 @@ def run(steps: list, exists: str = "erase", tmp: str | None = None,
         elif name == "summed_area_table":
             params = {}
             log(f"{i}: summed_area_table {src} ({info.data_type} {list(info.shape)}) -> {dst}")
+        elif name in POINTWISE:
+            own = ("offset", "shape", "multiply", "add", "add_first", "min", "max", "value",
+                   "replace")
+            params = {"args": {k: step[k] for k in own if step.get(k) is not None}}
+            log(f"{i}: {name} {params['args']} {src} ({info.data_type} {list(info.shape)}) "
+                f"-> {dst}")
+            enc = step_encoding(step, info.data_type)  # equal: bool, fill value false
         else:
             params = {"stride": list(f.stride), "discrete": bool(step.get("discrete", False))}
             log(f"{i}: downsample stride={params['stride']} discrete={params['discrete']} "
@@ -646,6 +822,9 @@ def run(steps: list, exists: str = "erase", tmp: str | None = None,
         elif name == "summed_area_table":
             st = S.summed_area_table(src, dst, data_type=params["data_type"], device=device,
                                      encoding=enc, chunk_limit=limit)
+        elif name in POINTWISE:
+            st = _store_pointwise(name, src, dst, params["args"], data_type=params["data_type"],
+                                  device=device, encoding=enc, chunk_limit=limit)
         else:
             st = S.downsample(src, dst, params["stride"], discrete=params["discrete"],
                               data_type=params["data_type"], device=device, encoding=enc,
@@ -686,7 +865,8 @@ def run(steps: list, exists: str = "erase", tmp: str | None = None,
             res = None
             if j > i:
                 threads = chunk_limit or 0
-                res = run_device_chain(steps[i:j + 1], paths, device, threads, log)
+                res = run_device_chain(steps[i:j + 1], paths, device, threads, log,
+                                       fuse_pointwise=fuse_pointwise)
                 if res is not None and stats:
                     for k, st in enumerate(res):
                         log(json.dumps({"step": i + k, "filter": steps[i + k].get("filter"), **st}))
@@ -723,7 +903,8 @@ def main(argv=None) -> int:
         return 2
     try:
         run(steps, a.exists, a.tmp, a.chunk_limit, a.device, a.stats,
-            device_chain=not a.no_device_chain, gpus=a.gpus)
+            device_chain=not a.no_device_chain, gpus=a.gpus,
+            fuse_pointwise=not a.no_pointwise_fusion)
     except _abi.FilterError as e:
         print(f"Error: {e}", file=sys.stderr)
         return 1
