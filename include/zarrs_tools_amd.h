@@ -337,6 +337,40 @@ int zt_pointwise_apply_ndarray(zt_ctx* ctx, int dtype_in, const void* in, const 
                                int ndim, const int64_t* sub_start, const int64_t* sub_shape,
                                const zt_pointwise_op* ops, int n_ops, void* out);
 
+/* ---- zarrs_info reductions (src/info/range.rs, src/info/histogram.rs) ------------------------ */
+
+/* The 12 numeric types; ZT_BOOL is ZT_ERR_UNSUPPORTED_DATA_TYPE (the reference reaches
+ * `unimplemented!` there, range.rs:92-95, histogram.rs:32-35). */
+int zt_range_is_compatible(int dtype);
+int zt_histogram_is_compatible(int dtype);
+/* The range of an array (calculate_range, range.rs:99-131, with the meaning its documentation
+ * gives it: the smallest and the largest element; as written the reference seeds min with the
+ * type's minimum and max with its maximum, :113-116, so neither moves). Integers are compared
+ * exactly; NaN elements are ignored (PartialOrd, :115-116); -0.0 orders below +0.0; the
+ * infinities are values. `state` is 16 bytes of device memory, 8-byte aligned, that accumulates
+ * across calls: zt_range_init empties it, zt_range_accumulate folds n contiguous device elements
+ * (element alignment; n == 0 is a no-op) into it on the context's stream. */
+int zt_range_init(zt_ctx* ctx, void* state);
+int zt_range_accumulate(zt_ctx* ctx, int dtype, const void* in, int64_t n, void* state);
+/* Waits for the stream and reads the state back: *none = 1 when no non-NaN element was folded
+ * (min_bits / max_bits are then 0), else the smallest and largest element as storage bits of
+ * `dtype`, zero-extended (as zt_pointwise_op's element immediates). */
+int zt_range_finish(zt_ctx* ctx, int dtype, const void* state, uint64_t* min_bits,
+                    uint64_t* max_bits, int* none);
+/* calculate_histogram's per-element work (histogram.rs:51-68): for every one of n contiguous
+ * device elements x, in f64 with one rounding per operation,
+ *   norm = (x as f64 - min) / (max - min);  bin = min(floor(max(norm * n_bins, 0)) as usize,
+ *   n_bins - 1)
+ * and hist[bin] += 1 on the device array hist (uint64[n_bins], which the caller zeroes; calls
+ * accumulate). NaN elements and the 0 / 0 of max == min land in bin 0, +inf in the last bin.
+ * n_bins in [1, 2^30], min and max finite, or ZT_ERR_INVALID_PARAMETERS (the reference
+ * underflows n_bins - 1 at n_bins == 0). n == 0 is a no-op. */
+int zt_histogram_accumulate(zt_ctx* ctx, int dtype, const void* in, int64_t n, int64_t n_bins,
+                            double min, double max, uint64_t* hist);
+/* bin_edges[i] = (i as f64 / n_bins as f64) * (max - min) + min for i in 0..=n_bins
+ * (histogram.rs:62-68), n_bins + 1 host doubles. Host only. */
+int zt_histogram_bin_edges(int64_t n_bins, double min, double max, double* edges);
+
 /* ---- Zarr V3 store -> store path (host storage in and out) ----------------------------------
  * The reference's filters read and write Zarr arrays through zarrs (Array::retrieve_array_subset_
  * ndarray / store_array_subset_ndarray, guided_filter.rs:95-110; zarrs_ome.rs:226-232). These
@@ -493,6 +527,22 @@ int zt_store_downsample_gaussian(const char* in_path, const char* out_path, cons
                                  int dtype_out, const char* encoding_json, int device,
                                  int64_t row_begin, int64_t row_end, int nthreads, int flags,
                                  zt_store_stats* stats);
+/* zarrs_info PATH range / histogram N_BINS MIN MAX over a store (zarrs_info.rs:170-197;
+ * calculate_range range.rs:99-131, calculate_histogram histogram.rs:37-75): the decode -> H2D
+ * ring of the filters with no output array, the reduction of zt_range_accumulate /
+ * zt_histogram_accumulate on every input chunk row [row_begin, row_end) along axis 0 (row_end
+ * < 0 = all) and one small D2H at the end. Only the elements inside the array's shape count (the
+ * reference also counts the stored padding of edge chunks, retrieve_chunk_elements, range.rs:112,
+ * histogram.rs:54); a chunk absent from the store counts as its fill value. Results over disjoint
+ * row ranges combine to the whole: histograms add, ranges fold. Progress counts input chunks.
+ * zt_store_range: *dtype the array's type, the rest as zt_range_finish. zt_store_histogram:
+ * hist is n_bins host uint64, overwritten. */
+int zt_store_range(const char* path, int device, int64_t row_begin, int64_t row_end, int nthreads,
+                   int* dtype, uint64_t* min_bits, uint64_t* max_bits, int* none,
+                   zt_store_stats* stats);
+int zt_store_histogram(const char* path, int64_t n_bins, double min, double max, int device,
+                       int64_t row_begin, int64_t row_end, int nthreads, uint64_t* hist,
+                       zt_store_stats* stats);
 /* 1 if the named codec can be read and written here, else 0. */
 int zt_store_codec_available(const char* name);
 /* Host bytes the store pipeline budgets 80 % of (the available-memory half of

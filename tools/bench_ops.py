@@ -12,6 +12,10 @@ write per voxel: the streaming yardstick).
 `--only pointwise`: the per-element filters (reencode, crop, rescale, clamp, equal, replace_value)
 on 1024^3, each single launch alternated with the reencode cast of the same type pair, and the
 fused rescale -> clamp -> equal chain against its three single launches.
+`--only info`: zarrs_info's range and histogram (info.hip) on 1024^3 uint8, uint16 and float32,
+each alternated with the pointwise reencode of the same type on the same volume (the per-byte
+yardstick); the histogram at 256 and 4096 bins and at 65 536 bins (above the LDS cap), on uniform
+noise and on a volume that is 90 % one value.
 
 Algorithmic bytes: pyramid = level 0 read once + every level written once (2 B per u16
 element; the fused launches never read an intermediate level back); Gaussian = 4 B read + 4 B written per voxel (the separable passes' intermediates are
@@ -410,6 +414,120 @@ def bench_pointwise(n, rounds=5, window_s=0.25):
     return out
 
 
+def bench_info(n, rounds=3, window_s=0.25):
+    """zarrs_info's reductions on n^3, device-resident (info.hip): per input type the range, the
+    histogram at 256 bins (LDS bins, 16 replicas, plain adds), 4096 bins (LDS bins, one replica,
+    leader rounds) and 65 536 bins (global bins, leader rounds), each histogram on uniform
+    noise and on a copy of it in which 90 % of the elements, scattered, hold one value, alternated
+    in one run with the pointwise reencode of the same type on the same volume (one read and one
+    write per element: the per-byte yardstick). Windows of at least window_s after a warm-up.
+    Bytes: the elements read. One JSON line per type; every result is checked (sum(hist) == n^3;
+    a sampled block against tests/info_ref.py)."""
+    import math
+    import numpy as np
+    import torch
+    import zarrs_tools_amd as zt
+    from tests import info_ref as R
+    from tests.gpu_util import from_dev
+    ctx = zt.default_context(0)
+    stream = torch.cuda.current_stream()
+    total = n ** 3
+    m = 1 << 16  # the sampled check: the first m elements
+
+    def measure(ops):
+        reps = {}
+        for k, fn in ops.items():  # warm-up, then calls per window until it lasts window_s
+            r = 1
+            while True:
+                t = timed(fn, stream, r)
+                if t * r >= window_s * 1e3:
+                    break
+                r = math.ceil(window_s * 1e3 / t * 1.05) + 1
+            reps[k] = r
+        ms = {k: [] for k in ops}
+        for _ in range(rounds):
+            for k, fn in ops.items():
+                ms[k].append(timed(fn, stream, reps[k]))
+        return ms, reps
+
+    def line(v, r, nbytes):
+        v = sorted(v)
+        med = v[len(v) // 2]
+        gbs = nbytes / (med / 1e3) / 1e9
+        return {"ms": round(med, 4), "ms_min": round(v[0], 4), "ms_max": round(v[-1], 4),
+                "spread": round((v[-1] - v[0]) / med, 4), "calls_per_window": r,
+                "bytes_read": nbytes, "GB/s": round(gbs, 1),
+                "hbm_frac": round(gbs / HBM_PEAK_GBS, 4)}
+
+    out = []
+    for dt in ("uint8", "uint16", "float32"):
+        if dt == "float32":
+            x, mn, mx, const = zt.synth_step_noise_f32((n, n, n)), 0.0, 600.0, 40.0
+        else:
+            u16 = zt.synth_u16((n, n, n))
+            x, mn, mx, const = u16, 0.0, 65535.0, 40
+            if dt == "uint8":
+                x = zt.Rescale(255.0 / 65535.0, 0.0).apply_ndarray(u16, dtype_out="uint8")
+                mx = 255.0
+                del u16
+        x90 = x.clone().reshape(-1)
+        for i in range(0, total, 1 << 28):  # 90 % of the elements, scattered, hold `const`
+            part = x90[i:i + (1 << 28)]
+            if dt == "uint16":  # (masked assignment through the signed view of the same bits)
+                part = part.view(torch.int16)
+            part[torch.rand(part.numel(), device=x.device) < 0.9] = const
+        x90 = x90.reshape(x.shape)
+        torch.cuda.empty_cache()
+        y = torch.empty_like(x)
+        prog = zt.PointwiseProgram([zt.Reencode()], dt, [dt], x.shape)
+        rng_op = zt.Range()
+        rstate = rng_op.new_state(x.device, ctx)
+        hists = {nb: zt.Histogram(nb, mn, mx) for nb in (256, 4096, 65536)}
+        hstate = {nb: h.new_state(x.device) for nb, h in hists.items()}
+        ops = {"reencode": lambda: prog.run(x, y, ctx),
+               "range": lambda: rng_op.accumulate(x, rstate, ctx)}
+        for nb, h in hists.items():
+            for name, src in (("noise", x), ("90pct", x90)):
+                ops[f"histogram_{nb}_{name}"] = (
+                    lambda h=h, src=src, nb=nb: h.accumulate(src, hstate[nb], ctx))
+        # checks: whole-volume counts, and a sampled block against the restatement
+        checks = {}
+        for nb, h in hists.items():
+            for name, src in (("noise", x), ("90pct", x90)):
+                _, hist = h.apply_ndarray(src, ctx)
+                _, part = h.apply_ndarray(src.reshape(-1)[:m], ctx)
+                ref = R.histogram(from_dev(src.reshape(-1)[:m], dt), dt, nb, mn, mx)[1]
+                checks[f"histogram_{nb}_{name}"] = bool(int(hist.sum()) == total and
+                                                        np.array_equal(part, ref))
+        got = rng_op.apply_ndarray(x.reshape(-1)[:m], ctx)
+        checks["range"] = bool(got == R.range_(from_dev(x.reshape(-1)[:m], dt), dt))
+        ms, reps = measure(ops)
+        nbytes = total * x.element_size()
+        yard = line(ms["reencode"], reps["reencode"], nbytes)
+        yard["bytes_written"] = nbytes
+        res = {"op": f"zarrs_info range / histogram on {dt} (device-resident)",
+               "config": {"shape": [n] * 3, "rounds": rounds, "window_s": window_s,
+                          "histogram_min_max": [mn, mx]},
+               "range_whole_volume": list(rng_op.apply_ndarray(x, ctx)),
+               "yardstick": {"op": f"pointwise reencode {dt} -> {dt}, same volume, windows "
+                                   "alternated (reads and writes every element)", **yard},
+               "ops": {}}
+        for k in ops:
+            if k == "reencode":
+                continue
+            ln = line(ms[k], reps[k], nbytes)
+            ln["exact"] = checks[k]
+            ln["ratio_to_reencode_per_byte_read"] = round(ln["ms"] / yard["ms"], 4)
+            res["ops"][k] = ln
+        for nb in hists:
+            a, b = res["ops"][f"histogram_{nb}_noise"], res["ops"][f"histogram_{nb}_90pct"]
+            b["ratio_to_noise"] = round(b["ms"] / a["ms"], 4)
+        out.append(res)
+        del x, x90, y, hstate
+        torch.cuda.empty_cache()
+    return out
+
+
 def bench_guided4d(shape, chunk, radius, reps):
     """Config T per GPU: a (T, Z, Y, X) f32 time-series share, chunks
     (4, 256, 256, 256), eps 2500. 4-D arrays take the separable per-axis path."""
@@ -546,6 +664,9 @@ def main():
             print(json.dumps(bench_sat(a.gaussian_size, din, dout)), flush=True)
     if "pointwise" in only:  # each with its reencode-cast yardstick, alternated
         for res in bench_pointwise(a.gaussian_size):
+            print(json.dumps(res), flush=True)
+    if "info" in only:  # each with its pointwise-reencode yardstick, alternated
+        for res in bench_info(a.gaussian_size):
             print(json.dumps(res), flush=True)
 
 

@@ -21,11 +21,15 @@ from .filter import (  # noqa: E402
     Gaussian,
     GradientMagnitude,
     GuidedFilter,
+    Histogram,
     PointwiseProgram,
+    Range,
     Reencode,
     ReplaceValue,
     Rescale,
     SummedAreaTable,
+    combine_histograms,
+    combine_ranges,
     default_context,
     dtype_of,
     pyramid,
@@ -45,4 +49,5 @@ __all__ = [
     "default_context", "dtype_of", "lib", "octant_assignment", "OctantAssignment", "pyramid",
     "pyramid_level_shapes", "slab_assignment",
     "synth_step_noise_f32", "synth_u16", "synth_box", "torch_dtype",
+    "Histogram", "Range", "combine_histograms", "combine_ranges",
 ]

@@ -137,6 +137,7 @@ def lib() -> ctypes.CDLL:
     vp = ctypes.c_void_p
     c_int, c_float = ctypes.c_int, ctypes.c_float
     fp = ctypes.POINTER(ctypes.c_float)
+    u64p = ctypes.POINTER(ctypes.c_uint64)
     sig = {
         "zt_abi_version": ([], c_int),
         "zt_last_error": ([], ctypes.c_char_p),
@@ -202,6 +203,21 @@ def lib() -> ctypes.CDLL:
                                 ctypes.POINTER(PointwiseOp), c_int, i64p, i64p, c_int,
                                 ctypes.c_int64, ctypes.c_int64, c_int, c_int,
                                 ctypes.POINTER(StoreStats)], c_int),
+        "zt_range_is_compatible": ([c_int], c_int),
+        "zt_histogram_is_compatible": ([c_int], c_int),
+        "zt_range_init": ([vp, vp], c_int),
+        "zt_range_accumulate": ([vp, c_int, vp, ctypes.c_int64, vp], c_int),
+        "zt_range_finish": ([vp, c_int, vp, u64p, u64p, ctypes.POINTER(c_int)], c_int),
+        "zt_histogram_accumulate": ([vp, c_int, vp, ctypes.c_int64, ctypes.c_int64,
+                                     ctypes.c_double, ctypes.c_double, vp], c_int),
+        "zt_histogram_bin_edges": ([ctypes.c_int64, ctypes.c_double, ctypes.c_double,
+                                    ctypes.POINTER(ctypes.c_double)], c_int),
+        "zt_store_range": ([ctypes.c_char_p, c_int, ctypes.c_int64, ctypes.c_int64, c_int,
+                            ctypes.POINTER(c_int), u64p, u64p, ctypes.POINTER(c_int),
+                            ctypes.POINTER(StoreStats)], c_int),
+        "zt_store_histogram": ([ctypes.c_char_p, ctypes.c_int64, ctypes.c_double,
+                                ctypes.c_double, c_int, ctypes.c_int64, ctypes.c_int64, c_int,
+                                u64p, ctypes.POINTER(StoreStats)], c_int),
         "zt_synth_step_noise_f32": ([vp, vp, i64p, c_int, i64p, ctypes.c_int64, ctypes.c_uint64],
                                     c_int),
         "zt_synth_u16": ([vp, vp, i64p, c_int, i64p, ctypes.c_int64, ctypes.c_uint64], c_int),

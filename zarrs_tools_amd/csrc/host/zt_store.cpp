@@ -848,9 +848,243 @@ void run_pipeline(const Array& in, const Array& out, int device, int64_t row_beg
     }
 }
 
+// The input half of run_pipeline for a reduction (zarrs_info's range and histogram): the input
+// chunk rows [row_begin, row_end) along axis 0 are decoded once into a ring of pinned host rows,
+// copied to one of two device slabs and handed to `reduce` (slab, element count) on the compute
+// stream; there is no output array. A row buffer holds the part of its chunks inside the array's
+// shape, so the padding of edge chunks is never seen. Progress steps count input chunks.
+void run_reduce_pipeline(const Array& in, int device, int64_t row_begin, int64_t row_end,
+                         int nthreads,
+                         const std::function<int(zt_ctx*, const void* slab, int64_t n)>& reduce,
+                         const std::function<int(zt_ctx*)>& begin,
+                         const std::function<int(zt_ctx*)>& finish, zt_store_stats* st) {
+    const auto t_start = Clock::now();
+    const int nd = in.ndim();
+    const int64_t in_cz = in.chunk_shape[0], nz = in.shape[0];
+    const int64_t rows_total = (nz + in_cz - 1) / in_cz;
+    row_begin = std::max<int64_t>(0, row_begin);
+    row_end = row_end < 0 ? rows_total : std::min(row_end, rows_total);
+    int64_t in_plane = 1;
+    for (int d = 1; d < nd; ++d) in_plane *= in.shape[d];
+    const bool empty = row_begin >= row_end || in_plane == 0;
+    const size_t in_pb = (size_t)in_plane * in.esz;
+    const uint64_t in_row_b = (uint64_t)in_cz * in_pb;
+    // memory budget and --chunk-limit, as run_pipeline: NR decoded rows, NB device slabs
+    int64_t NR = 3;
+    int NB = 2;
+    const uint64_t host_budget = host_available_bytes() / 10 * 8;
+    while (!empty && NR * in_row_b > host_budget) {
+        if (NR > 1) --NR;
+        else throw zt::zarr::Error(ZT_ERR_OUT_OF_MEMORY, kNotEnoughMemory);
+    }
+    const int64_t in_row_chunks = (int64_t)chunks_in_rows(in, 0, 1).size();
+    int threads = resolve_threads(nthreads);
+    if (g_chunk_limit > 0) {
+        while (NR > 1 && NR * in_row_chunks > g_chunk_limit) --NR;
+        threads = (int)std::max<int64_t>(1, std::min<int64_t>(threads, g_chunk_limit));
+    }
+    if (hipSetDevice(device) != hipSuccess)
+        throw zt::zarr::Error(ZT_ERR_DEVICE, "hipSetDevice failed");
+    if (!empty) {
+        const uint64_t dev_budget = device_available_bytes() / 10 * 8;
+        if ((uint64_t)NB * in_row_b > dev_budget) NB = 1;
+        if ((uint64_t)NB * in_row_b > dev_budget)
+            throw zt::zarr::Error(ZT_ERR_OUT_OF_MEMORY, kNotEnoughMemory);
+    }
+    Ctx ctx;
+    if (int rc = zt_ctx_create(device, &ctx.c)) throw zt::zarr::Error(rc, zt_last_error());
+    Streams streams;
+    hipStream_t s_h2d = streams.make(), s_comp = streams.make();
+    if (int rc = zt_ctx_set_stream(ctx.c, s_comp)) throw zt::zarr::Error(rc, zt_last_error());
+    if (int rc = begin(ctx.c)) throw zt::zarr::Error(rc, zt_last_error());
+    Events E;
+    hipEvent_t ev_h2d0[2], ev_h2d[2], ev_k0[2], ev_k[2];
+    for (int s = 0; s < 2; ++s) {
+        ev_h2d0[s] = E.make(); ev_h2d[s] = E.make(); ev_k0[s] = E.make(); ev_k[s] = E.make();
+    }
+    bool slot_used[2] = {false, false};
+    std::vector<hipEvent_t> ring_ev(NR);
+    std::vector<bool> ring_ev_set(NR, false);
+    for (auto& e : ring_ev) e = E.make();
+    std::vector<Pinned> hin(NR);
+    DevBuf dslab[2];
+    if (!empty) {
+        for (auto& h : hin) h.alloc((size_t)in_cz * in_pb);
+        for (int s = 0; s < NB; ++s) dslab[s].alloc((size_t)in_cz * in_pb);
+    }
+    Pool pool(threads);
+    std::vector<Group> dec_group(NR);
+    std::vector<int64_t> ring_row(NR, -1);
+    std::atomic<uint64_t> bytes_read{0};
+    std::atomic<int64_t> dec_ns{0}, k_us{0}, chunks_done{0};
+    double h2d_ms = 0, k_ms = 0;
+    const int64_t chunks_total = empty ? 0 : (row_end - row_begin) * in_row_chunks;
+    std::vector<int64_t> in_row_shape(in.shape);
+    in_row_shape[0] = in_cz;
+    const std::vector<int64_t> in_row_st = c_strides(in_row_shape);
+
+    auto submit_decode = [&](int64_t j) {
+        const int64_t s = j % NR;
+        if (ring_row[s] >= 0) {
+            dec_group[s].wait();
+            if (ring_ev_set[s]) HIPCHK(hipEventSynchronize(ring_ev[s]));  // H2D done reading it
+        }
+        ring_row[s] = j;
+        uint8_t* buf = hin[s].u8();
+        for (auto& idx : chunks_in_rows(in, j, j + 1)) {
+            pool.submit(dec_group[s], [&, idx, buf, j] {
+                const auto t0 = Clock::now();
+                std::vector<int64_t> origin(nd, 0);
+                origin[0] = j * in_cz;
+                size_t n = in.read_chunk(idx.data(), buf, origin.data(), in_row_shape.data(),
+                                         in_row_st.data());
+                bytes_read += n;
+                dec_ns += (int64_t)(secs_since(t0) * 1e9);
+                std::lock_guard<std::mutex> lk(g_progress_mu);
+                const int64_t step = ++chunks_done;
+                if (g_progress_fn) {
+                    zt_progress pr{};
+                    pr.step = step;
+                    pr.num_steps = chunks_total;
+                    pr.read_s = dec_ns.load() * 1e-9;
+                    pr.process_s = k_us.load() * 1e-6;
+                    g_progress_fn(&pr, g_progress_user);
+                }
+            });
+        }
+    };
+    // the device times of the row that last used slot s (its kernel has to be over anyway before
+    // the slab is written again)
+    auto collect = [&](int s) {
+        if (!slot_used[s]) return;
+        HIPCHK(hipEventSynchronize(ev_k[s]));
+        h2d_ms += ev_ms(ev_h2d0[s], ev_h2d[s]);
+        const float km = ev_ms(ev_k0[s], ev_k[s]);
+        k_ms += km;
+        k_us += (int64_t)(km * 1e3f);
+        slot_used[s] = false;
+    };
+    int64_t voxels = 0;
+    try {
+        int64_t next_dec = row_begin;
+        for (int64_t j = row_begin; !empty && j < row_end; ++j) {
+            while (next_dec < row_end && next_dec - NR < j) submit_decode(next_dec++);
+            dec_group[j % NR].wait();
+            const int s = (int)(j % NB);
+            collect(s);
+            const int64_t planes = std::min((j + 1) * in_cz, nz) - j * in_cz;
+            HIPCHK(hipEventRecord(ev_h2d0[s], s_h2d));
+            HIPCHK(hipMemcpyAsync(dslab[s].p, hin[j % NR].p, (size_t)planes * in_pb,
+                                  hipMemcpyHostToDevice, s_h2d));
+            HIPCHK(hipEventRecord(ev_h2d[s], s_h2d));
+            HIPCHK(hipEventRecord(ring_ev[j % NR], s_h2d));
+            ring_ev_set[j % NR] = true;
+            HIPCHK(hipStreamWaitEvent(s_comp, ev_h2d[s], 0));
+            HIPCHK(hipEventRecord(ev_k0[s], s_comp));
+            if (int rc = reduce(ctx.c, dslab[s].p, planes * in_plane))
+                throw zt::zarr::Error(rc, zt_last_error());
+            HIPCHK(hipEventRecord(ev_k[s], s_comp));
+            slot_used[s] = true;
+            voxels += planes * in_plane;
+        }
+        for (auto& g : dec_group) g.wait();
+        collect(0);
+        collect(1);
+        if (int rc = finish(ctx.c)) throw zt::zarr::Error(rc, zt_last_error());
+    } catch (...) {
+        for (auto& g : dec_group) g.wait_nothrow();
+        (void)hipDeviceSynchronize();
+        throw;
+    }
+    if (st) {
+        st->wall_s = secs_since(t_start);
+        st->decode_s = dec_ns.load() * 1e-9;
+        st->h2d_s = h2d_ms * 1e-3;
+        st->kernel_s = k_ms * 1e-3;
+        st->bytes_read = bytes_read.load();
+        st->voxels = (uint64_t)voxels;
+        st->rows = empty ? 0 : row_end - row_begin;
+        st->threads = pool.size();
+        st->rows_in_flight = (int)NR;
+        st->double_buffered = NB == 2;
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+int zt_store_range(const char* path, int device, int64_t row_begin, int64_t row_end, int nthreads,
+                   int* dtype, uint64_t* min_bits, uint64_t* max_bits, int* none,
+                   zt_store_stats* stats) {
+    try {
+        if (!path || !min_bits || !max_bits || !none)
+            return zt::set_last_error(ZT_ERR_INVALID_PARAMETERS, "null argument");
+        if (stats) *stats = zt_store_stats{};
+        Array in = Array::open(path);
+        if (dtype) *dtype = in.dtype;
+        if (int rc = zt_range_is_compatible(in.dtype)) return rc;
+        const int dt = in.dtype;
+        DevBuf state;
+        run_reduce_pipeline(
+            in, device, row_begin, row_end, nthreads,
+            [&](zt_ctx* c, const void* slab, int64_t n) {
+                return zt_range_accumulate(c, dt, slab, n, state.p);
+            },
+            [&](zt_ctx* c) {
+                state.alloc(16);
+                return zt_range_init(c, state.p);
+            },
+            [&](zt_ctx* c) { return zt_range_finish(c, dt, state.p, min_bits, max_bits, none); },
+            stats);
+        return ZT_OK;
+    } catch (const std::exception& e) {
+        return report(e);
+    }
+}
+
+int zt_store_histogram(const char* path, int64_t n_bins, double min, double max, int device,
+                       int64_t row_begin, int64_t row_end, int nthreads, uint64_t* hist,
+                       zt_store_stats* stats) {
+    try {
+        if (!path) return zt::set_last_error(ZT_ERR_INVALID_PARAMETERS, "null argument");
+        if (stats) *stats = zt_store_stats{};
+        // the arguments first (n_bins, min, max), then the array's type: no device work yet
+        if (n_bins < 1 || n_bins > ((int64_t)1 << 30) || !std::isfinite(min) || !std::isfinite(max))
+            return zt::set_last_error(ZT_ERR_INVALID_PARAMETERS,
+                                      "histogram: n_bins in [1, 2^30], min and max finite");
+        if (!hist) return zt::set_last_error(ZT_ERR_INVALID_PARAMETERS, "null argument");
+        Array in = Array::open(path);
+        if (int rc = zt_histogram_is_compatible(in.dtype)) return rc;
+        const int dt = in.dtype;
+        DevBuf dhist;
+        run_reduce_pipeline(
+            in, device, row_begin, row_end, nthreads,
+            [&](zt_ctx* c, const void* slab, int64_t n) {
+                return zt_histogram_accumulate(c, dt, slab, n, n_bins, min, max,
+                                               static_cast<uint64_t*>(dhist.p));
+            },
+            [&](zt_ctx* c) -> int {
+                dhist.alloc((size_t)n_bins * 8);
+                void* s = nullptr;
+                if (int rc = zt_ctx_get_stream(c, &s)) return rc;
+                HIPCHK(hipMemsetAsync(dhist.p, 0, (size_t)n_bins * 8, (hipStream_t)s));
+                return ZT_OK;
+            },
+            [&](zt_ctx* c) -> int {
+                void* s = nullptr;
+                if (int rc = zt_ctx_get_stream(c, &s)) return rc;
+                HIPCHK(hipMemcpyAsync(hist, dhist.p, (size_t)n_bins * 8, hipMemcpyDeviceToHost,
+                                      (hipStream_t)s));
+                HIPCHK(hipStreamSynchronize((hipStream_t)s));
+                return ZT_OK;
+            },
+            stats);
+        return ZT_OK;
+    } catch (const std::exception& e) {
+        return report(e);
+    }
+}
 
 int zt_store_array_info(const char* path, int* dtype, int* ndim, int64_t* shape,
                         int64_t* chunk_shape, int64_t* inner_chunk_shape) {

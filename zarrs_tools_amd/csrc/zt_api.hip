@@ -1331,6 +1331,110 @@ int zt_pointwise_apply_ndarray(zt_ctx* ctx, int dtype_in, const void* in, const 
     return ZT_OK;
 }
 
+// ---- zarrs_info reductions (range.rs, histogram.rs) --------------------------------------------
+
+namespace {
+
+// the 12 numeric types; bool is `unimplemented!` in the reference (range.rs:92-95,
+// histogram.rs:32-35)
+int info_dtype_ok(int dtype) {
+    if (!valid_dtype(dtype))
+        return fail(ZT_ERR_UNSUPPORTED_DATA_TYPE, "Unsupported data type code %d", dtype);
+    if (dtype == ZT_BOOL) return fail(ZT_ERR_UNSUPPORTED_DATA_TYPE, "Unsupported data type bool");
+    return ZT_OK;
+}
+
+int info_run_ok(int dtype, const void* in, int64_t n) {
+    if (n < 0) return fail(ZT_ERR_INVALID_PARAMETERS, "negative element count");
+    if (n > 0 && !in) return fail(ZT_ERR_INVALID_PARAMETERS, "null data pointer");
+    if (((uintptr_t)in % zt::dtype_size(dtype)) != 0)
+        return fail(ZT_ERR_INVALID_PARAMETERS, "data pointers must be element aligned");
+    return ZT_OK;
+}
+
+int histogram_args_ok(int64_t n_bins, double mn, double mx) {
+    if (n_bins < 1 || n_bins > zt::kInfoMaxBins)
+        return fail(ZT_ERR_INVALID_PARAMETERS, "n_bins %lld not in [1, %lld]", (long long)n_bins,
+                    (long long)zt::kInfoMaxBins);
+    if (!std::isfinite(mn) || !std::isfinite(mx))
+        return fail(ZT_ERR_INVALID_PARAMETERS, "histogram min and max must be finite");
+    return ZT_OK;
+}
+
+}  // namespace
+
+int zt_range_is_compatible(int dtype) { return info_dtype_ok(dtype); }
+int zt_histogram_is_compatible(int dtype) { return info_dtype_ok(dtype); }
+
+int zt_range_init(zt_ctx* ctx, void* state) {
+    if (int rc = check_ctx(ctx)) return rc;
+    if (!state || ((uintptr_t)state % 8) != 0)
+        return fail(ZT_ERR_INVALID_PARAMETERS, "the range state is 16 device bytes, 8-byte aligned");
+    DeviceGuard guard(ctx->device);
+    hipError_t e = zt::launch_range_init(state, ctx->cur);
+    if (e != hipSuccess) return hip_fail(e, "range init launch");
+    return ZT_OK;
+}
+
+int zt_range_accumulate(zt_ctx* ctx, int dtype, const void* in, int64_t n, void* state) {
+    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = info_dtype_ok(dtype)) return rc;
+    if (int rc = info_run_ok(dtype, in, n)) return rc;
+    if (!state || ((uintptr_t)state % 8) != 0)
+        return fail(ZT_ERR_INVALID_PARAMETERS, "the range state is 16 device bytes, 8-byte aligned");
+    if (n == 0) return ZT_OK;
+    DeviceGuard guard(ctx->device);
+    if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev0, ctx->cur));
+    hipError_t e = zt::launch_range_accumulate(in, dtype, n, state, ctx->cur);
+    if (e != hipSuccess) return hip_fail(e, "range launch");
+    if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev1, ctx->cur));
+    return ZT_OK;
+}
+
+int zt_range_finish(zt_ctx* ctx, int dtype, const void* state, uint64_t* min_bits,
+                    uint64_t* max_bits, int* none) {
+    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = info_dtype_ok(dtype)) return rc;
+    if (!state || !min_bits || !max_bits || !none)
+        return fail(ZT_ERR_INVALID_PARAMETERS, "null pointer");
+    DeviceGuard guard(ctx->device);
+    uint64_t keys[2] = {0, 0};
+    ZT_HIP(hipMemcpyAsync(keys, state, sizeof keys, hipMemcpyDeviceToHost, ctx->cur));
+    ZT_HIP(hipStreamSynchronize(ctx->cur));
+    *none = keys[0] > keys[1] ? 1 : 0;
+    *min_bits = *max_bits = 0;
+    if (!*none) {
+        zt::range_decode(dtype, keys[0], min_bits);
+        zt::range_decode(dtype, keys[1], max_bits);
+    }
+    return ZT_OK;
+}
+
+int zt_histogram_accumulate(zt_ctx* ctx, int dtype, const void* in, int64_t n, int64_t n_bins,
+                            double min, double max, uint64_t* hist) {
+    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = info_dtype_ok(dtype)) return rc;
+    if (int rc = histogram_args_ok(n_bins, min, max)) return rc;
+    if (int rc = info_run_ok(dtype, in, n)) return rc;
+    if (!hist || ((uintptr_t)hist % 8) != 0)
+        return fail(ZT_ERR_INVALID_PARAMETERS, "hist is n_bins device uint64, 8-byte aligned");
+    if (n == 0) return ZT_OK;
+    DeviceGuard guard(ctx->device);
+    if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev0, ctx->cur));
+    hipError_t e = zt::launch_histogram_accumulate(in, dtype, n, n_bins, min, max, hist, ctx->cur);
+    if (e != hipSuccess) return hip_fail(e, "histogram launch");
+    if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev1, ctx->cur));
+    return ZT_OK;
+}
+
+int zt_histogram_bin_edges(int64_t n_bins, double min, double max, double* edges) {
+    if (int rc = histogram_args_ok(n_bins, min, max)) return rc;
+    if (!edges) return fail(ZT_ERR_INVALID_PARAMETERS, "null pointer");
+    const double range = max - min, nb = (double)n_bins;  // histogram.rs:62-68
+    for (int64_t i = 0; i <= n_bins; ++i) edges[i] = ((double)i / nb) * range + min;
+    return ZT_OK;
+}
+
 // ---- downsample ------------------------------------------------------------------------------
 
 int zt_downsample_is_compatible(int dtype_in, int dtype_out, int discrete) {

@@ -195,6 +195,25 @@ int pointwise_max_blocks();
 hipError_t launch_pointwise(const void* in, void* out, PwGeom g, const PwProgram& prog,
                             hipStream_t s);
 
+// zarrs_info reductions (info.hip; src/info/range.rs, src/info/histogram.rs) over a contiguous
+// run of n elements of `dtype` (the 12 numeric types) at element alignment.
+// Range: `state` is two device u64 words (smallest key, largest key) that accumulate across
+// calls; launch_range_init makes them (all ones, 0) = "none". range_decode turns a key of the
+// state back into the element's storage bits (zero-extended). NaN elements are ignored and
+// -0.0 orders below +0.0.
+// Histogram: adds into the device u64 hist[n_bins] the count of the elements of each bin,
+// bin = min(floor(max((x as f64 - min) / (max - min) * n_bins, 0)) as usize, n_bins - 1)
+// (histogram.rs:51-68). Up to kInfoLdsBins bins are privatised per workgroup in LDS.
+constexpr int kInfoLdsBins = 4096;               // u32 LDS bins of a workgroup (16 KiB)
+constexpr int64_t kInfoMaxBins = (int64_t)1 << 30;
+int info_max_blocks();
+hipError_t launch_range_init(void* state, hipStream_t s);
+hipError_t launch_range_accumulate(const void* in, int dtype, int64_t n, void* state,
+                                   hipStream_t s);
+void range_decode(int dtype, uint64_t key, uint64_t* bits);
+hipError_t launch_histogram_accumulate(const void* in, int dtype, int64_t n, int64_t n_bins,
+                                       double mn, double mx, uint64_t* hist, hipStream_t s);
+
 // Synthetic inputs
 hipError_t launch_synth_step_noise_f32(float* out, int64_t n, int64_t plane, int64_t nx_row,
                                        int64_t nx_global, int64_t z0, uint64_t seed,

@@ -15,6 +15,8 @@ Names, argument meaning and error behaviour follow LDeakin/zarrs_tools 0.7.2:
   - ``Reencode``, ``Crop``, ``Rescale``, ``Clamp``, ``Equal``, ``ReplaceValue`` <-
     src/filter/filters/{reencode,crop,rescale,clamp,equal,replace_value}.rs (the per-element
     filters; ``PointwiseProgram`` runs consecutive ones as one launch)
+  - ``Range``, ``Histogram`` <- src/info/range.rs, src/info/histogram.rs (zarrs_info's
+    reductions; ``combine_ranges`` / ``combine_histograms`` join partial results)
   - ``ArraySubsetOverlap`` <- src/filter/array_subset_overlap.rs:4-52
 Arrays are device-resident torch tensors (torch is used only for device memory and streams);
 every computation runs in libzarrs_tools_amd.so through the C ABI.
@@ -808,6 +810,174 @@ class PointwiseProgram:
         out = torch.empty(tuple(self.shape), dtype=torch_dtype(self.dtype_out), device=v.device)
         self.run(v, out, ctx)
         return out
+
+
+def element_value(bits: int, dtype: str):
+    """An element given as its storage bits (zero-extended; the inverse of element_bits) as a
+    Python value: integers as int, the float types widened exactly to f64 as float."""
+    import struct
+    if dtype in _INT_BITS:
+        n = _INT_BITS[dtype]
+        bits &= (1 << n) - 1
+        return bits - (1 << n) if dtype[0] == "i" and bits >> (n - 1) else bits
+    if dtype == "float64":
+        return struct.unpack("<d", struct.pack("<Q", bits))[0]
+    if dtype == "float32":
+        return struct.unpack("<f", struct.pack("<I", bits & 0xFFFFFFFF))[0]
+    if dtype == "float16":
+        return struct.unpack("<e", struct.pack("<H", bits & 0xFFFF))[0]
+    if dtype == "bfloat16":
+        return struct.unpack("<f", struct.pack("<I", (bits & 0xFFFF) << 16))[0]
+    raise _abi.UnsupportedDataType(_abi.ERR_UNSUPPORTED_DATA_TYPE,
+                                   f"Unsupported data type {dtype}")
+
+
+def _info_dtype(dtype: str) -> int:
+    if dtype not in DTYPES:
+        raise _abi.UnsupportedDataType(_abi.ERR_UNSUPPORTED_DATA_TYPE,
+                                       f"Unsupported data type {dtype}")
+    return DTYPES[dtype]
+
+
+def _info_run(v):
+    """(contiguous device tensor, data type name) of a tensor or DeviceArray."""
+    if isinstance(v, DeviceArray):
+        return v.data.contiguous(), v.dtype
+    return v.contiguous(), dtype_of(v)
+
+
+def _order_key(x):
+    """Orders -0.0 below +0.0 (the kernels' key order); integers as they are."""
+    return (x, math.copysign(1.0, x)) if isinstance(x, float) else (x, 0)
+
+
+def combine_ranges(parts):
+    """The range of the union of parts that each gave (min, max), (None, None) for a part with
+    no non-NaN element: ranges fold."""
+    los = [p[0] for p in parts if p[0] is not None]
+    his = [p[1] for p in parts if p[1] is not None]
+    if not los:
+        return None, None
+    return min(los, key=_order_key), max(his, key=_order_key)
+
+
+def combine_histograms(parts):
+    """The histogram of the union of parts that each gave (bin_edges, hist) for the same n_bins,
+    min and max: histograms add."""
+    import numpy as np
+    parts = list(parts)
+    if not parts:
+        raise _invalid("combine_histograms: no parts")
+    edges = np.asarray(parts[0][0], dtype=np.float64)
+    hist = np.zeros(len(edges) - 1, dtype=np.uint64)
+    for e, h in parts:
+        if len(e) != len(edges) or not np.array_equal(np.asarray(e), edges):
+            raise _invalid("combine_histograms: the parts' bin edges differ")
+        hist += np.asarray(h, dtype=np.uint64)
+    return edges, hist
+
+
+class Range:
+    """src/info/range.rs — calculate_range with the meaning its documentation gives it (the
+    smallest and largest element; NaN ignored, -0.0 below +0.0, integers exact). The 12 numeric
+    types; bool is UnsupportedDataType (`unimplemented!`, range.rs:92-95)."""
+
+    def name(self) -> str:
+        return "range"
+
+    def is_compatible(self, dtype: str) -> None:
+        check(lib().zt_range_is_compatible(_info_dtype(dtype)))
+
+    def new_state(self, device=None, ctx: Optional[Context] = None):
+        """An empty device state (16 bytes) that `accumulate` folds arrays into."""
+        torch = _torch()
+        state = torch.empty(2, dtype=torch.int64, device="cuda" if device is None else device)
+        ctx = ctx or default_context(state.device.index)
+        check(lib().zt_range_init(ctx.handle, _ptr(state)))
+        return state
+
+    def accumulate(self, v, state, ctx: Optional[Context] = None) -> None:
+        x, dtype = _info_run(v)
+        ctx = ctx or default_context(x.device.index)
+        check(lib().zt_range_accumulate(ctx.handle, _info_dtype(dtype), _ptr(x), x.numel(),
+                                        _ptr(state)))
+
+    def finish(self, state, dtype: str, ctx: Optional[Context] = None):
+        """(min, max) of everything folded into `state` as elements of `dtype`, or (None, None)."""
+        ctx = ctx or default_context(state.device.index)
+        lo, hi, none = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_int()
+        check(lib().zt_range_finish(ctx.handle, _info_dtype(dtype), _ptr(state), ctypes.byref(lo),
+                                    ctypes.byref(hi), ctypes.byref(none)))
+        if none.value:
+            return None, None
+        return element_value(lo.value, dtype), element_value(hi.value, dtype)
+
+    def apply_ndarray(self, v, ctx: Optional[Context] = None):
+        """(min, max) of a device tensor or DeviceArray; (None, None) when it has no non-NaN
+        element."""
+        x, dtype = _info_run(v)
+        self.is_compatible(dtype)
+        ctx = ctx or default_context(x.device.index)
+        state = self.new_state(x.device, ctx)
+        self.accumulate(v, state, ctx)
+        return self.finish(state, dtype, ctx)
+
+
+class Histogram:
+    """src/info/histogram.rs — calculate_histogram(n_bins, min, max): per element, in f64,
+    bin = min(floor(max((x - min) / (max - min) * n_bins, 0)), n_bins - 1) (:51-68). n_bins == 0
+    and a non-finite min or max raise InvalidParameters."""
+
+    def __init__(self, n_bins: int, min: float, max: float):
+        self.n_bins, self.min, self.max = int(n_bins), float(min), float(max)
+        self._edges = self._bin_edges()
+
+    def name(self) -> str:
+        return "histogram"
+
+    def is_compatible(self, dtype: str) -> None:
+        check(lib().zt_histogram_is_compatible(_info_dtype(dtype)))
+
+    def _bin_edges(self):
+        import numpy as np
+        n = self.n_bins if 0 < self.n_bins <= (1 << 30) else 0
+        edges = np.empty(n + 1, dtype=np.float64)
+        check(lib().zt_histogram_bin_edges(
+            self.n_bins, self.min, self.max,
+            edges.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+        return edges
+
+    def bin_edges(self):
+        """histogram.rs:62-68: n_bins + 1 f64 edges."""
+        return self._edges.copy()
+
+    def new_state(self, device=None):
+        """A zeroed device histogram (n_bins u64 counts, held as int64) for `accumulate`."""
+        torch = _torch()
+        return torch.zeros(self.n_bins, dtype=torch.int64,
+                           device="cuda" if device is None else device)
+
+    def accumulate(self, v, hist, ctx: Optional[Context] = None) -> None:
+        x, dtype = _info_run(v)
+        ctx = ctx or default_context(x.device.index)
+        if hist.numel() != self.n_bins or not hist.is_contiguous() or hist.element_size() != 8:
+            raise _invalid("histogram state: n_bins contiguous 8-byte counts")
+        check(lib().zt_histogram_accumulate(ctx.handle, _info_dtype(dtype), _ptr(x), x.numel(),
+                                            self.n_bins, self.min, self.max, _ptr(hist)))
+
+    def finish(self, hist):
+        """(bin_edges, hist as np.uint64) of a device state."""
+        import numpy as np
+        return self.bin_edges(), hist.cpu().numpy().view(np.uint64).copy()
+
+    def apply_ndarray(self, v, ctx: Optional[Context] = None):
+        """(bin_edges: np.float64[n_bins + 1], hist: np.uint64[n_bins]) of a device tensor or
+        DeviceArray."""
+        x, dtype = _info_run(v)
+        self.is_compatible(dtype)
+        hist = self.new_state(x.device)
+        self.accumulate(v, hist, ctx)
+        return self.finish(hist)
 
 
 class Downsample:

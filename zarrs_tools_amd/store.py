@@ -461,6 +461,49 @@ def replace_value(input_path, output_path, value, replace, data_type: Optional[s
                           finish=finish, chunk_limit=chunk_limit)
 
 
+def range(path, device: int = 0, rows=None, nthreads: int = 0, chunk_limit: int = 0,
+          stats: Optional[dict] = None):
+    """zarrs_info PATH range over a store (zt_store_range): (min, max) of the elements inside the
+    array's shape as Python values (int, or float widened to f64), (None, None) when there is no
+    non-NaN element. `rows` = (begin, end) input chunk rows along axis 0 (None = all): partial
+    results combine with filter.combine_ranges. `stats`: a dict that receives the run stats."""
+    from .filter import element_value
+    set_chunk_limit(chunk_limit)
+    st = _abi.StoreStats()
+    r0, r1 = (0, -1) if rows is None else (int(rows[0]), int(rows[1]))
+    dt, none = ctypes.c_int(-1), ctypes.c_int()
+    lo, hi = ctypes.c_uint64(), ctypes.c_uint64()
+    check(lib().zt_store_range(_b(path), int(device), r0, r1, int(nthreads), ctypes.byref(dt),
+                               ctypes.byref(lo), ctypes.byref(hi), ctypes.byref(none),
+                               ctypes.byref(st)))
+    if stats is not None:
+        stats.update(st.as_dict())
+    if none.value:
+        return None, None
+    name = DTYPE_NAMES[dt.value]
+    return element_value(lo.value, name), element_value(hi.value, name)
+
+
+def histogram(path, n_bins: int, min: float, max: float, device: int = 0, rows=None,
+              nthreads: int = 0, chunk_limit: int = 0, stats: Optional[dict] = None):
+    """zarrs_info PATH histogram N_BINS MIN MAX over a store (zt_store_histogram): (bin_edges:
+    np.float64[n_bins + 1], hist: np.uint64[n_bins]). `rows` as `range`: partial results combine
+    with filter.combine_histograms."""
+    from .filter import Histogram
+    edges = Histogram(n_bins, min, max).bin_edges()  # validates n_bins, min, max
+    set_chunk_limit(chunk_limit)
+    st = _abi.StoreStats()
+    r0, r1 = (0, -1) if rows is None else (int(rows[0]), int(rows[1]))
+    hist = np.zeros(int(n_bins), dtype=np.uint64)
+    check(lib().zt_store_histogram(_b(path), int(n_bins), float(min), float(max), int(device),
+                                   r0, r1, int(nthreads),
+                                   hist.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                                   ctypes.byref(st)))
+    if stats is not None:
+        stats.update(st.as_dict())
+    return edges, hist
+
+
 def downsample_gaussian(input_path, output_path, stride, sigma, kernel_half_size,
                         data_type: Optional[str] = None, device: int = 0, rows=None,
                         nthreads: int = 0, erase: bool = True, finish: bool = True,
