@@ -371,6 +371,23 @@ int zt_histogram_accumulate(zt_ctx* ctx, int dtype, const void* in, int64_t n, i
  * (histogram.rs:62-68), n_bins + 1 host doubles. Host only. */
 int zt_histogram_bin_edges(int64_t n_bins, double min, double max, double* edges);
 
+/* ---- zarrs_validate comparison (src/bin/zarrs_validate.rs) ----------------------------------- */
+
+/* The per-element work of zarrs_validate (`bytes_first == bytes_second`, zarrs_validate.rs:
+ * 145-147): two contiguous device runs of n elements of one data type (all 13 types) compared by
+ * their storage bits, so a NaN equals a NaN with the same bits only, +0.0 differs from -0.0 and
+ * bool is a byte. `state` is 16 bytes of device memory, 8-byte aligned, that accumulates across
+ * calls: the number of differing elements and the smallest differing element index.
+ * zt_compare_init empties it; zt_compare_accumulate folds a and b (element alignment, which may
+ * differ between the two; n == 0 is a no-op) into it on the context's stream, an element's index
+ * being `base` (>= 0) plus its index in the run. */
+int zt_compare_init(zt_ctx* ctx, void* state);
+int zt_compare_accumulate(zt_ctx* ctx, int dtype, const void* a, const void* b, int64_t n,
+                          int64_t base, void* state);
+/* Waits for the stream and reads the state back: *n_diff the number of differing elements,
+ * *first the smallest differing index, -1 when the runs were equal (zarrs_validate.rs:147). */
+int zt_compare_finish(zt_ctx* ctx, const void* state, uint64_t* n_diff, int64_t* first);
+
 /* ---- Zarr V3 store -> store path (host storage in and out) ----------------------------------
  * The reference's filters read and write Zarr arrays through zarrs (Array::retrieve_array_subset_
  * ndarray / store_array_subset_ndarray, guided_filter.rs:95-110; zarrs_ome.rs:226-232). These
@@ -543,6 +560,22 @@ int zt_store_range(const char* path, int device, int64_t row_begin, int64_t row_
 int zt_store_histogram(const char* path, int64_t n_bins, double min, double max, int device,
                        int64_t row_begin, int64_t row_end, int nthreads, uint64_t* hist,
                        zt_store_stats* stats);
+/* zarrs_validate FIRST SECOND over two stores (zarrs_validate.rs:90-157). Shape, then data type
+ * are checked before any device work: ZT_ERR_INVALID_PARAMETERS with the reference's messages
+ * `Array shapes do not match: [..] vs [..]` and `Array data types do not match: A vs B`
+ * (:101-113); encoding and attributes are ignored. Then the decode -> H2D ring of zt_store_range
+ * with two inputs: for every chunk row [row_begin, row_end) of the FIRST array along axis 0
+ * (row_end < 0 = all) the chunks of both arrays that meet the row are decoded into two rows of
+ * one shape (a chunk of the second array taller than a row is decoded once per row it meets, as
+ * retrieve_array_subset per first-array chunk does, :146) and compared by zt_compare_accumulate.
+ * Only the elements inside the shape count; a chunk absent from a store counts as that array's
+ * fill value. *n_diff is the number of differing elements, *first the C-order index in the whole
+ * array of the first of them, -1 when there is none. Results over disjoint row ranges combine to
+ * the whole: counts add, the first index is the minimum. Progress counts the chunks of both
+ * arrays. */
+int zt_store_compare(const char* first_path, const char* second_path, int device,
+                     int64_t row_begin, int64_t row_end, int nthreads, uint64_t* n_diff,
+                     int64_t* first, zt_store_stats* stats);
 /* 1 if the named codec can be read and written here, else 0. */
 int zt_store_codec_available(const char* name);
 /* Host bytes the store pipeline budgets 80 % of (the available-memory half of

@@ -16,6 +16,9 @@ fused rescale -> clamp -> equal chain against its three single launches.
 each alternated with the pointwise reencode of the same type on the same volume (the per-byte
 yardstick); the histogram at 256 and 4096 bins and at 65 536 bins (above the LDS cap), on uniform
 noise and on a volume that is 90 % one value.
+`--only compare`: zarrs_validate's comparison (compare.hip) on two 1024^3 float32 arrays, equal,
+1 % differing and all differing, alternated with the range over one float32 run of the same
+bytes.
 
 Algorithmic bytes: pyramid = level 0 read once + every level written once (2 B per u16
 element; the fused launches never read an intermediate level back); Gaussian = 4 B read + 4 B written per voxel (the separable passes' intermediates are
@@ -528,6 +531,85 @@ def bench_info(n, rounds=3, window_s=0.25):
     return out
 
 
+def bench_compare(n, rounds=5, window_s=0.4):
+    """zarrs_validate's comparison on two n^3 float32 device arrays (compare.hip): an equal pair
+    (the ballot fast path), a pair in which 1 % of the elements, scattered, differ and a pair in
+    which every element differs (no fast path), alternated in one run with the range over one
+    float32 run of 2 n^3 elements. The equal pair is the two halves of that run, so both read the
+    same bytes; `compare_equal_apart` is the first half against a copy allocated on its own (the
+    halves lie exactly 4 n^3 bytes apart, a power of two at n = 1024). Windows of at least window_s after a warm-up, `rounds` of each, medians. Bytes:
+    the elements read (both arrays). Every result is checked exactly."""
+    import math
+    import torch
+    import zarrs_tools_amd as zt
+    ctx = zt.default_context(0)
+    stream = torch.cuda.current_stream()
+    total = n ** 3
+    big = torch.empty(2 * total, dtype=torch.float32, device="cuda")
+    big[:total] = zt.synth_step_noise_f32((n, n, n)).reshape(-1)
+    big[total:] = big[:total]
+    a, b = big[:total], big[total:]
+    b_apart, b1, b_all = a.clone(), a.clone(), a.clone()
+    n1, first1 = 0, None
+    for i in range(0, total, 1 << 28):  # 1 % of the elements, scattered: the lowest bit flipped
+        part = b1[i:i + (1 << 28)].view(torch.int32)
+        mask = torch.rand(part.numel(), device=part.device) < 0.01
+        part[mask] ^= 1
+        n1 += int(mask.sum())
+        if first1 is None and bool(mask.any()):
+            first1 = i + int(torch.nonzero(mask)[0])
+        b_all[i:i + (1 << 28)].view(torch.int32).bitwise_xor_(1)
+        del mask
+    torch.cuda.empty_cache()
+    cmp_op, rng_op = zt.Compare(), zt.Range()
+    cstate, rstate = cmp_op.new_state(a.device, ctx), rng_op.new_state(a.device, ctx)
+    checks = {"compare_equal": cmp_op.apply_ndarray(a, b, ctx) == (0, None),
+              "compare_equal_apart": cmp_op.apply_ndarray(a, b_apart, ctx) == (0, None),
+              "compare_1pct": cmp_op.apply_ndarray(a, b1, ctx) == (n1, first1),
+              "compare_all": cmp_op.apply_ndarray(a, b_all, ctx) == (total, 0)}
+    ops = {"range": lambda: rng_op.accumulate(big, rstate, ctx),
+           "compare_equal": lambda: cmp_op.accumulate(a, b, cstate, 0, ctx),
+           "compare_equal_apart": lambda: cmp_op.accumulate(a, b_apart, cstate, 0, ctx),
+           "compare_1pct": lambda: cmp_op.accumulate(a, b1, cstate, 0, ctx),
+           "compare_all": lambda: cmp_op.accumulate(a, b_all, cstate, 0, ctx)}
+    reps = {}
+    for k, fn in ops.items():  # warm-up, then calls per window until it lasts window_s
+        r = 1
+        while True:
+            t = timed(fn, stream, r)
+            if t * r >= window_s * 1e3:
+                break
+            r = math.ceil(window_s * 1e3 / t * 1.05) + 1
+        reps[k] = r
+    ms = {k: [] for k in ops}
+    for _ in range(rounds):
+        for k, fn in ops.items():
+            ms[k].append(timed(fn, stream, reps[k]))
+    nbytes = 2 * total * 4
+    res = {"op": "zarrs_validate compare on two float32 arrays (device-resident)",
+           "config": {"shape": [n] * 3, "rounds": rounds, "window_s": window_s,
+                      "differing_1pct": n1,
+                      "address_distance": {"compare_equal": b.data_ptr() - a.data_ptr(),
+                                           "compare_equal_apart": b_apart.data_ptr() - a.data_ptr(),
+                                           "compare_1pct": b1.data_ptr() - a.data_ptr(),
+                                           "compare_all": b_all.data_ptr() - a.data_ptr()}},
+           "ops": {}}
+    for k in ops:
+        v = sorted(ms[k])
+        med = v[len(v) // 2]
+        gbs = nbytes / (med / 1e3) / 1e9
+        res["ops"][k] = {"ms": round(med, 4), "ms_min": round(v[0], 4), "ms_max": round(v[-1], 4),
+                         "spread": round((v[-1] - v[0]) / med, 4), "calls_per_window": reps[k],
+                         "bytes_read": nbytes, "GB/s": round(gbs, 1),
+                         "GiB/s": round(nbytes / (med / 1e3) / 2 ** 30, 1),
+                         "hbm_frac": round(gbs / HBM_PEAK_GBS, 4)}
+        if k != "range":
+            res["ops"][k]["exact"] = bool(checks[k])
+    for k in ops:
+        res["ops"][k]["ratio_to_range"] = round(res["ops"][k]["ms"] / res["ops"]["range"]["ms"], 4)
+    return res
+
+
 def bench_guided4d(shape, chunk, radius, reps):
     """Config T per GPU: a (T, Z, Y, X) f32 time-series share, chunks
     (4, 256, 256, 256), eps 2500. 4-D arrays take the separable per-axis path."""
@@ -668,6 +750,8 @@ def main():
     if "info" in only:  # each with its pointwise-reencode yardstick, alternated
         for res in bench_info(a.gaussian_size):
             print(json.dumps(res), flush=True)
+    if "compare" in only:  # with the range over the same bytes, alternated
+        print(json.dumps(bench_compare(a.gaussian_size)), flush=True)
 
 
 if __name__ == "__main__":

@@ -13,6 +13,7 @@ from .filter import (  # noqa: E402
     ArraySubset,
     ArraySubsetOverlap,
     Clamp,
+    Compare,
     Context,
     Crop,
     DeviceArray,
@@ -28,6 +29,7 @@ from .filter import (  # noqa: E402
     ReplaceValue,
     Rescale,
     SummedAreaTable,
+    combine_compares,
     combine_histograms,
     combine_ranges,
     default_context,
@@ -50,4 +52,5 @@ __all__ = [
     "pyramid_level_shapes", "slab_assignment",
     "synth_step_noise_f32", "synth_u16", "synth_box", "torch_dtype",
     "Histogram", "Range", "combine_histograms", "combine_ranges",
+    "Compare", "combine_compares",
 ]

@@ -218,6 +218,12 @@ def lib() -> ctypes.CDLL:
         "zt_store_histogram": ([ctypes.c_char_p, ctypes.c_int64, ctypes.c_double,
                                 ctypes.c_double, c_int, ctypes.c_int64, ctypes.c_int64, c_int,
                                 u64p, ctypes.POINTER(StoreStats)], c_int),
+        "zt_compare_init": ([vp, vp], c_int),
+        "zt_compare_accumulate": ([vp, c_int, vp, vp, ctypes.c_int64, ctypes.c_int64, vp], c_int),
+        "zt_compare_finish": ([vp, vp, u64p, ctypes.POINTER(ctypes.c_int64)], c_int),
+        "zt_store_compare": ([ctypes.c_char_p, ctypes.c_char_p, c_int, ctypes.c_int64,
+                              ctypes.c_int64, c_int, u64p, ctypes.POINTER(ctypes.c_int64),
+                              ctypes.POINTER(StoreStats)], c_int),
         "zt_synth_step_noise_f32": ([vp, vp, i64p, c_int, i64p, ctypes.c_int64, ctypes.c_uint64],
                                     c_int),
         "zt_synth_u16": ([vp, vp, i64p, c_int, i64p, ctypes.c_int64, ctypes.c_uint64], c_int),

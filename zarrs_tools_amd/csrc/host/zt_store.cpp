@@ -28,6 +28,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <vector>
 
 #include "../../../include/zarrs_tools_amd.h"
@@ -853,9 +854,16 @@ void run_pipeline(const Array& in, const Array& out, int device, int64_t row_beg
 // copied to one of two device slabs and handed to `reduce` (slab, element count) on the compute
 // stream; there is no output array. A row buffer holds the part of its chunks inside the array's
 // shape, so the padding of edge chunks is never seen. Progress steps count input chunks.
-void run_reduce_pipeline(const Array& in, int device, int64_t row_begin, int64_t row_end,
-                         int nthreads,
-                         const std::function<int(zt_ctx*, const void* slab, int64_t n)>& reduce,
+// With a second array `in2` of the same shape and type (zarrs_validate): rows stay the first
+// array's; every ring slot holds a pinned row of each array and every device slot two slabs (the
+// budgets count both); the chunks of in2 that meet the row's planes are decoded into a row of the
+// same shape (read_chunk clips to it), so a chunk of in2 taller than a row is decoded once per
+// row it meets; `reduce` gets both slabs (slab2 is null without in2) and the C-order index in the
+// whole array of the row's first element; progress counts the chunks of both arrays.
+void run_reduce_pipeline(const Array& in, const Array* in2, int device, int64_t row_begin,
+                         int64_t row_end, int nthreads,
+                         const std::function<int(zt_ctx*, const void* slab, const void* slab2,
+                                                 int64_t n, int64_t base)>& reduce,
                          const std::function<int(zt_ctx*)>& begin,
                          const std::function<int(zt_ctx*)>& finish, zt_store_stats* st) {
     const auto t_start = Clock::now();
@@ -868,7 +876,14 @@ void run_reduce_pipeline(const Array& in, int device, int64_t row_begin, int64_t
     for (int d = 1; d < nd; ++d) in_plane *= in.shape[d];
     const bool empty = row_begin >= row_end || in_plane == 0;
     const size_t in_pb = (size_t)in_plane * in.esz;
-    const uint64_t in_row_b = (uint64_t)in_cz * in_pb;
+    // (with a second array, a row of each)
+    const uint64_t in_row_b = (uint64_t)in_cz * in_pb * (in2 ? 2 : 1);
+    // the chunk rows of in2 that meet row j of `in`
+    auto rows2 = [&](int64_t j, int64_t& r0, int64_t& r1) {
+        const int64_t cz2 = in2->chunk_shape[0];
+        r0 = j * in_cz / cz2;
+        r1 = (std::min((j + 1) * in_cz, nz) + cz2 - 1) / cz2;
+    };
     // memory budget and --chunk-limit, as run_pipeline: NR decoded rows, NB device slabs
     int64_t NR = 3;
     int NB = 2;
@@ -878,9 +893,21 @@ void run_reduce_pipeline(const Array& in, int device, int64_t row_begin, int64_t
         else throw zt::zarr::Error(ZT_ERR_OUT_OF_MEMORY, kNotEnoughMemory);
     }
     const int64_t in_row_chunks = (int64_t)chunks_in_rows(in, 0, 1).size();
+    // chunks decoded for one row (the most, with in2) and for all rows
+    int64_t row_chunks_max = in_row_chunks;
+    int64_t chunks_total = empty ? 0 : (row_end - row_begin) * in_row_chunks;
+    if (in2 && !empty) {
+        const int64_t per2 = (int64_t)chunks_in_rows(*in2, 0, 1).size();
+        for (int64_t j = row_begin; j < row_end; ++j) {
+            int64_t r0, r1;
+            rows2(j, r0, r1);
+            row_chunks_max = std::max(row_chunks_max, in_row_chunks + (r1 - r0) * per2);
+            chunks_total += (r1 - r0) * per2;
+        }
+    }
     int threads = resolve_threads(nthreads);
     if (g_chunk_limit > 0) {
-        while (NR > 1 && NR * in_row_chunks > g_chunk_limit) --NR;
+        while (NR > 1 && NR * row_chunks_max > g_chunk_limit) --NR;
         threads = (int)std::max<int64_t>(1, std::min<int64_t>(threads, g_chunk_limit));
     }
     if (hipSetDevice(device) != hipSuccess)
@@ -906,11 +933,13 @@ void run_reduce_pipeline(const Array& in, int device, int64_t row_begin, int64_t
     std::vector<hipEvent_t> ring_ev(NR);
     std::vector<bool> ring_ev_set(NR, false);
     for (auto& e : ring_ev) e = E.make();
-    std::vector<Pinned> hin(NR);
-    DevBuf dslab[2];
+    std::vector<Pinned> hin(NR), hin2(in2 ? NR : 0);
+    DevBuf dslab[2], dslab2[2];
     if (!empty) {
         for (auto& h : hin) h.alloc((size_t)in_cz * in_pb);
+        for (auto& h : hin2) h.alloc((size_t)in_cz * in_pb);
         for (int s = 0; s < NB; ++s) dslab[s].alloc((size_t)in_cz * in_pb);
+        for (int s = 0; in2 && s < NB; ++s) dslab2[s].alloc((size_t)in_cz * in_pb);
     }
     Pool pool(threads);
     std::vector<Group> dec_group(NR);
@@ -918,7 +947,6 @@ void run_reduce_pipeline(const Array& in, int device, int64_t row_begin, int64_t
     std::atomic<uint64_t> bytes_read{0};
     std::atomic<int64_t> dec_ns{0}, k_us{0}, chunks_done{0};
     double h2d_ms = 0, k_ms = 0;
-    const int64_t chunks_total = empty ? 0 : (row_end - row_begin) * in_row_chunks;
     std::vector<int64_t> in_row_shape(in.shape);
     in_row_shape[0] = in_cz;
     const std::vector<int64_t> in_row_st = c_strides(in_row_shape);
@@ -930,14 +958,25 @@ void run_reduce_pipeline(const Array& in, int device, int64_t row_begin, int64_t
             if (ring_ev_set[s]) HIPCHK(hipEventSynchronize(ring_ev[s]));  // H2D done reading it
         }
         ring_row[s] = j;
-        uint8_t* buf = hin[s].u8();
-        for (auto& idx : chunks_in_rows(in, j, j + 1)) {
-            pool.submit(dec_group[s], [&, idx, buf, j] {
+        // (array, chunk index, row buffer) of every chunk that meets row j
+        std::vector<std::tuple<const Array*, std::vector<int64_t>, uint8_t*>> jobs;
+        for (auto& idx : chunks_in_rows(in, j, j + 1)) jobs.emplace_back(&in, idx, hin[s].u8());
+        if (in2) {
+            int64_t r0, r1;
+            rows2(j, r0, r1);
+            for (auto& idx : chunks_in_rows(*in2, r0, r1))
+                jobs.emplace_back(in2, idx, hin2[s].u8());
+        }
+        for (auto& job : jobs) {
+            const Array* arr = std::get<0>(job);
+            const std::vector<int64_t> idx = std::get<1>(job);
+            uint8_t* buf = std::get<2>(job);
+            pool.submit(dec_group[s], [&, arr, idx, buf, j] {
                 const auto t0 = Clock::now();
                 std::vector<int64_t> origin(nd, 0);
                 origin[0] = j * in_cz;
-                size_t n = in.read_chunk(idx.data(), buf, origin.data(), in_row_shape.data(),
-                                         in_row_st.data());
+                size_t n = arr->read_chunk(idx.data(), buf, origin.data(), in_row_shape.data(),
+                                           in_row_st.data());
                 bytes_read += n;
                 dec_ns += (int64_t)(secs_since(t0) * 1e9);
                 std::lock_guard<std::mutex> lk(g_progress_mu);
@@ -976,12 +1015,16 @@ void run_reduce_pipeline(const Array& in, int device, int64_t row_begin, int64_t
             HIPCHK(hipEventRecord(ev_h2d0[s], s_h2d));
             HIPCHK(hipMemcpyAsync(dslab[s].p, hin[j % NR].p, (size_t)planes * in_pb,
                                   hipMemcpyHostToDevice, s_h2d));
+            if (in2)
+                HIPCHK(hipMemcpyAsync(dslab2[s].p, hin2[j % NR].p, (size_t)planes * in_pb,
+                                      hipMemcpyHostToDevice, s_h2d));
             HIPCHK(hipEventRecord(ev_h2d[s], s_h2d));
             HIPCHK(hipEventRecord(ring_ev[j % NR], s_h2d));
             ring_ev_set[j % NR] = true;
             HIPCHK(hipStreamWaitEvent(s_comp, ev_h2d[s], 0));
             HIPCHK(hipEventRecord(ev_k0[s], s_comp));
-            if (int rc = reduce(ctx.c, dslab[s].p, planes * in_plane))
+            if (int rc = reduce(ctx.c, dslab[s].p, dslab2[s].p, planes * in_plane,
+                                j * in_cz * in_plane))
                 throw zt::zarr::Error(rc, zt_last_error());
             HIPCHK(hipEventRecord(ev_k[s], s_comp));
             slot_used[s] = true;
@@ -1027,8 +1070,8 @@ int zt_store_range(const char* path, int device, int64_t row_begin, int64_t row_
         const int dt = in.dtype;
         DevBuf state;
         run_reduce_pipeline(
-            in, device, row_begin, row_end, nthreads,
-            [&](zt_ctx* c, const void* slab, int64_t n) {
+            in, nullptr, device, row_begin, row_end, nthreads,
+            [&](zt_ctx* c, const void* slab, const void*, int64_t n, int64_t) {
                 return zt_range_accumulate(c, dt, slab, n, state.p);
             },
             [&](zt_ctx* c) {
@@ -1059,8 +1102,8 @@ int zt_store_histogram(const char* path, int64_t n_bins, double min, double max,
         const int dt = in.dtype;
         DevBuf dhist;
         run_reduce_pipeline(
-            in, device, row_begin, row_end, nthreads,
-            [&](zt_ctx* c, const void* slab, int64_t n) {
+            in, nullptr, device, row_begin, row_end, nthreads,
+            [&](zt_ctx* c, const void* slab, const void*, int64_t n, int64_t) {
                 return zt_histogram_accumulate(c, dt, slab, n, n_bins, min, max,
                                                static_cast<uint64_t*>(dhist.p));
             },
@@ -1080,6 +1123,48 @@ int zt_store_histogram(const char* path, int64_t n_bins, double min, double max,
                 return ZT_OK;
             },
             stats);
+        return ZT_OK;
+    } catch (const std::exception& e) {
+        return report(e);
+    }
+}
+
+int zt_store_compare(const char* first_path, const char* second_path, int device,
+                     int64_t row_begin, int64_t row_end, int nthreads, uint64_t* n_diff,
+                     int64_t* first, zt_store_stats* stats) {
+    try {
+        if (!first_path || !second_path || !n_diff || !first)
+            return zt::set_last_error(ZT_ERR_INVALID_PARAMETERS, "null argument");
+        if (stats) *stats = zt_store_stats{};
+        Array a = Array::open(first_path), b = Array::open(second_path);
+        // shape, then data type (zarrs_validate.rs:101-113): no device work yet
+        if (a.shape != b.shape) {
+            auto list = [](const std::vector<int64_t>& v) {  // `{:?}` of a Vec<u64>
+                std::string s = "[";
+                for (size_t i = 0; i < v.size(); ++i) s += (i ? ", " : "") + std::to_string(v[i]);
+                return s + "]";
+            };
+            return zt::set_last_error(
+                ZT_ERR_INVALID_PARAMETERS,
+                ("Array shapes do not match: " + list(a.shape) + " vs " + list(b.shape)).c_str());
+        }
+        if (a.dtype != b.dtype)
+            return zt::set_last_error(
+                ZT_ERR_INVALID_PARAMETERS,
+                (std::string("Array data types do not match: ") + zt::zarr::dtype_name(a.dtype) +
+                 " vs " + zt::zarr::dtype_name(b.dtype)).c_str());
+        const int dt = a.dtype;
+        DevBuf state;
+        run_reduce_pipeline(
+            a, &b, device, row_begin, row_end, nthreads,
+            [&](zt_ctx* c, const void* sa, const void* sb, int64_t n, int64_t base) {
+                return zt_compare_accumulate(c, dt, sa, sb, n, base, state.p);
+            },
+            [&](zt_ctx* c) {
+                state.alloc(16);
+                return zt_compare_init(c, state.p);
+            },
+            [&](zt_ctx* c) { return zt_compare_finish(c, state.p, n_diff, first); }, stats);
         return ZT_OK;
     } catch (const std::exception& e) {
         return report(e);

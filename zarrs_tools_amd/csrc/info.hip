@@ -1,7 +1,8 @@
 // info.hip — the whole-array reductions of zarrs_info: `range` (src/info/range.rs) and
 // `histogram` (src/info/histogram.rs), on a contiguous run of n elements.
 //
-// Both kernels read the run the same way. The run needs element alignment only (a device view may
+// Both kernels read the run the same way (zt_info.hpp, shared with compare.hip). The run needs
+// element alignment only (a device view may
 // start anywhere): the elements before the first 16-byte boundary (the head) and those after the
 // last whole 16-byte vector (the tail) are read one per lane by workgroup 0; the vectors in
 // between are read as aligned 16-byte loads, kInfoUnroll per lane and step, a step being
@@ -36,22 +37,16 @@
 #include <type_traits>
 
 #include "zt_device.hpp"
+#include "zt_info.hpp"
 #include "zt_kernels.hpp"
 
 namespace zt {
 
 namespace {
 
-constexpr int kInfoThreads = 256;
-constexpr int kInfoUnroll = 4;  // 16-byte vectors a lane loads per step
-constexpr int64_t kInfoStepVecs = (int64_t)kInfoThreads * kInfoUnroll;
 // A workgroup flushes its LDS bins after this many steps: at most 2^17 steps * 2^10 vectors * 16
 // elements = 2^31 elements (plus < 32 of head and tail) between flushes, so a u32 bin cannot wrap.
 constexpr int kInfoFlushSteps = 1 << 17;
-
-struct __attribute__((aligned(16))) Vec16A {
-    uint32_t w[4];
-};
 
 // ---- range ---------------------------------------------------------------------------------------
 
@@ -87,17 +82,6 @@ __device__ __forceinline__ bool range_key(T x, typename KeyOf<T>::type& k) {
     } else {
         k = x;
         return true;
-    }
-}
-
-template <typename K>
-__device__ __forceinline__ K shfl_xor_key(K v, int m) {
-    if constexpr (sizeof(K) == 4) {
-        return (K)__shfl_xor((unsigned)v, m, 64);
-    } else {
-        const unsigned lo = __shfl_xor((unsigned)v, m, 64);
-        const unsigned hi = __shfl_xor((unsigned)(v >> 32), m, 64);
-        return ((K)hi << 32) | lo;
     }
 }
 
@@ -328,34 +312,6 @@ __global__ __launch_bounds__(kInfoThreads) void hist_kernel(const T* p, int64_t 
         if (lane == 0 && pend_count) add(pend_bin, pend_count);
     }
     flush();
-}
-
-// The most workgroups of a kernel the device holds at once (0 if the runtime cannot tell).
-template <typename K>
-int resident_blocks(K kernel) {
-    int dev = 0, cus = 0, per_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kInfoThreads, 0) !=
-            hipSuccess) {
-        (void)hipGetLastError();
-        return 0;
-    }
-    return cus * per_cu;
-}
-
-// head elements, whole vectors and the grid of a run of n elements of `esz` bytes at p
-inline unsigned split_run(int resident, const void* p, int64_t n, int esz, int* head,
-                          int64_t* nvec) {
-    const int per = 16 / esz;
-    int64_t h = (int64_t)((16 - ((uintptr_t)p & 15)) & 15) / esz;
-    if (h > n) h = n;
-    *head = (int)h;
-    *nvec = (n - h) / per;
-    const int64_t steps = (*nvec + kInfoStepVecs - 1) / kInfoStepVecs;
-    int64_t cap = info_max_blocks();
-    if (resident > 0 && resident < cap) cap = resident;
-    return (unsigned)(steps < 1 ? 1 : steps < cap ? steps : cap);
 }
 
 template <typename T>

@@ -1435,6 +1435,59 @@ int zt_histogram_bin_edges(int64_t n_bins, double min, double max, double* edges
     return ZT_OK;
 }
 
+// ---- zarrs_validate comparison (zarrs_validate.rs:145-147) --------------------------------------
+
+namespace {
+
+int compare_state_ok(const void* state) {
+    if (!state || ((uintptr_t)state % 8) != 0)
+        return fail(ZT_ERR_INVALID_PARAMETERS,
+                    "the compare state is 16 device bytes, 8-byte aligned");
+    return ZT_OK;
+}
+
+}  // namespace
+
+int zt_compare_init(zt_ctx* ctx, void* state) {
+    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = compare_state_ok(state)) return rc;
+    DeviceGuard guard(ctx->device);
+    hipError_t e = zt::launch_compare_init(state, ctx->cur);
+    if (e != hipSuccess) return hip_fail(e, "compare init launch");
+    return ZT_OK;
+}
+
+int zt_compare_accumulate(zt_ctx* ctx, int dtype, const void* a, const void* b, int64_t n,
+                          int64_t base, void* state) {
+    if (int rc = check_ctx(ctx)) return rc;
+    if (!valid_dtype(dtype))
+        return fail(ZT_ERR_UNSUPPORTED_DATA_TYPE, "Unsupported data type code %d", dtype);
+    if (int rc = info_run_ok(dtype, a, n)) return rc;
+    if (int rc = info_run_ok(dtype, b, n)) return rc;
+    if (base < 0) return fail(ZT_ERR_INVALID_PARAMETERS, "negative base index");
+    if (int rc = compare_state_ok(state)) return rc;
+    if (n == 0) return ZT_OK;
+    DeviceGuard guard(ctx->device);
+    if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev0, ctx->cur));
+    hipError_t e = zt::launch_compare_accumulate(a, b, (int)zt::dtype_size(dtype), n, base, state,
+                                                 ctx->cur);
+    if (e != hipSuccess) return hip_fail(e, "compare launch");
+    if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev1, ctx->cur));
+    return ZT_OK;
+}
+
+int zt_compare_finish(zt_ctx* ctx, const void* state, uint64_t* n_diff, int64_t* first) {
+    if (int rc = check_ctx(ctx)) return rc;
+    if (!state || !n_diff || !first) return fail(ZT_ERR_INVALID_PARAMETERS, "null pointer");
+    DeviceGuard guard(ctx->device);
+    uint64_t words[2] = {0, 0};
+    ZT_HIP(hipMemcpyAsync(words, state, sizeof words, hipMemcpyDeviceToHost, ctx->cur));
+    ZT_HIP(hipStreamSynchronize(ctx->cur));
+    *n_diff = words[0];
+    *first = words[1] == ~(uint64_t)0 ? -1 : (int64_t)words[1];
+    return ZT_OK;
+}
+
 // ---- downsample ------------------------------------------------------------------------------
 
 int zt_downsample_is_compatible(int dtype_in, int dtype_out, int discrete) {

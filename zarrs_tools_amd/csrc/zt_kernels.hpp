@@ -214,6 +214,15 @@ void range_decode(int dtype, uint64_t key, uint64_t* bits);
 hipError_t launch_histogram_accumulate(const void* in, int dtype, int64_t n, int64_t n_bins,
                                        double mn, double mx, uint64_t* hist, hipStream_t s);
 
+// zarrs_validate's per-element work (compare.hip; src/bin/zarrs_validate.rs:145-147): two
+// contiguous runs a and b of n elements of `esz` bytes (1, 2, 4 or 8) at element alignment,
+// compared by their storage bits. `state` is two device u64 words (differing elements, smallest
+// differing index) that accumulate across calls; launch_compare_init makes them (0, all ones) =
+// "equal". `base` is added to the run-local index.
+hipError_t launch_compare_init(void* state, hipStream_t s);
+hipError_t launch_compare_accumulate(const void* a, const void* b, int esz, int64_t n,
+                                     int64_t base, void* state, hipStream_t s);
+
 // Synthetic inputs
 hipError_t launch_synth_step_noise_f32(float* out, int64_t n, int64_t plane, int64_t nx_row,
                                        int64_t nx_global, int64_t z0, uint64_t seed,

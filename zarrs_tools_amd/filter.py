@@ -17,6 +17,8 @@ Names, argument meaning and error behaviour follow LDeakin/zarrs_tools 0.7.2:
     filters; ``PointwiseProgram`` runs consecutive ones as one launch)
   - ``Range``, ``Histogram`` <- src/info/range.rs, src/info/histogram.rs (zarrs_info's
     reductions; ``combine_ranges`` / ``combine_histograms`` join partial results)
+  - ``Compare`` <- src/bin/zarrs_validate.rs:145-147 (the bitwise comparison of two arrays;
+    ``combine_compares`` joins partial results)
   - ``ArraySubsetOverlap`` <- src/filter/array_subset_overlap.rs:4-52
 Arrays are device-resident torch tensors (torch is used only for device memory and streams);
 every computation runs in libzarrs_tools_amd.so through the C ABI.
@@ -978,6 +980,75 @@ class Histogram:
         hist = self.new_state(x.device)
         self.accumulate(v, hist, ctx)
         return self.finish(hist)
+
+
+def combine_compares(parts):
+    """The comparison of the union of parts that each gave (n_diff, first_index | None) with
+    indices in the whole array: counts add, the first index is the minimum."""
+    parts = list(parts)
+    firsts = [p[1] for p in parts if p[1] is not None]
+    return sum(int(p[0]) for p in parts), (min(firsts) if firsts else None)
+
+
+class Compare:
+    """src/bin/zarrs_validate.rs:145-147 — `bytes_first == bytes_second`: two arrays of one shape
+    and data type compared by their storage bits (a NaN equals a NaN with the same bits only,
+    +0.0 differs from -0.0, bool is a byte). All 13 types. The result is (the number of differing
+    elements, the C-order index of the first or None)."""
+
+    def name(self) -> str:
+        return "compare"
+
+    def is_compatible(self, dtype_a: str, dtype_b: str) -> None:
+        _info_dtype(dtype_a), _info_dtype(dtype_b)
+        if dtype_a != dtype_b:  # zarrs_validate.rs:107-112
+            raise _invalid(f"Array data types do not match: {dtype_a} vs {dtype_b}")
+
+    def new_state(self, device=None, ctx: Optional[Context] = None):
+        """An empty device state (16 bytes) that `accumulate` folds pairs of arrays into."""
+        torch = _torch()
+        state = torch.empty(2, dtype=torch.int64, device="cuda" if device is None else device)
+        ctx = ctx or default_context(state.device.index)
+        check(lib().zt_compare_init(ctx.handle, _ptr(state)))
+        return state
+
+    def _pair(self, a, b):
+        """(contiguous a, contiguous b, data type) of two tensors or DeviceArrays of one shape,
+        data type and device."""
+        x, dtype = _info_run(a)
+        y, dtype_b = _info_run(b)
+        if tuple(x.shape) != tuple(y.shape):  # zarrs_validate.rs:101-106
+            raise _invalid(f"Array shapes do not match: {list(x.shape)} vs {list(y.shape)}")
+        self.is_compatible(dtype, dtype_b)
+        if x.device != y.device:
+            raise _invalid("compare: the two arrays are on different devices")
+        return x, y, dtype
+
+    def accumulate(self, a, b, state, base: int = 0, ctx: Optional[Context] = None) -> None:
+        """Folds the pair into `state`; an element's index is `base` plus its C-order index in
+        the pair."""
+        x, y, dtype = self._pair(a, b)
+        ctx = ctx or default_context(x.device.index)
+        check(lib().zt_compare_accumulate(ctx.handle, _info_dtype(dtype), _ptr(x), _ptr(y),
+                                          x.numel(), int(base), _ptr(state)))
+
+    def finish(self, state, ctx: Optional[Context] = None):
+        """(n_diff, first_index | None) of everything folded into `state`."""
+        ctx = ctx or default_context(state.device.index)
+        n_diff, first = ctypes.c_uint64(), ctypes.c_int64()
+        check(lib().zt_compare_finish(ctx.handle, _ptr(state), ctypes.byref(n_diff),
+                                      ctypes.byref(first)))
+        return n_diff.value, (None if first.value < 0 else first.value)
+
+    def apply_ndarray(self, a, b, ctx: Optional[Context] = None):
+        """(n_diff, first_index | None) of two device tensors or DeviceArrays; InvalidParameters
+        when their shapes or data types differ."""
+        x, y, dtype = self._pair(a, b)
+        ctx = ctx or default_context(x.device.index)
+        state = self.new_state(x.device, ctx)
+        check(lib().zt_compare_accumulate(ctx.handle, _info_dtype(dtype), _ptr(x), _ptr(y),
+                                          x.numel(), 0, _ptr(state)))
+        return self.finish(state, ctx)
 
 
 class Downsample:

@@ -504,6 +504,25 @@ def histogram(path, n_bins: int, min: float, max: float, device: int = 0, rows=N
     return edges, hist
 
 
+def compare(first, second, device: int = 0, rows=None, nthreads: int = 0, chunk_limit: int = 0,
+            stats: Optional[dict] = None):
+    """zarrs_validate FIRST SECOND over two stores (zt_store_compare): (n_diff, first_index) of
+    the elements inside the shape compared by their storage bits, first_index the C-order index
+    in the whole array or None when the arrays are equal. InvalidParameters with the reference's
+    message when the shapes or the data types differ (checked before any device work). `rows` =
+    (begin, end) chunk rows of the first array along axis 0 (None = all): partial results combine
+    with filter.combine_compares. `stats`: a dict that receives the run stats."""
+    set_chunk_limit(chunk_limit)
+    st = _abi.StoreStats()
+    r0, r1 = (0, -1) if rows is None else (int(rows[0]), int(rows[1]))
+    n_diff, idx = ctypes.c_uint64(), ctypes.c_int64()
+    check(lib().zt_store_compare(_b(first), _b(second), int(device), r0, r1, int(nthreads),
+                                 ctypes.byref(n_diff), ctypes.byref(idx), ctypes.byref(st)))
+    if stats is not None:
+        stats.update(st.as_dict())
+    return n_diff.value, (None if idx.value < 0 else idx.value)
+
+
 def downsample_gaussian(input_path, output_path, stride, sigma, kernel_half_size,
                         data_type: Optional[str] = None, device: int = 0, rows=None,
                         nthreads: int = 0, erase: bool = True, finish: bool = True,
