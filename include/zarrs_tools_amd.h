@@ -388,6 +388,25 @@ int zt_compare_accumulate(zt_ctx* ctx, int dtype, const void* a, const void* b, 
  * *first the smallest differing index, -1 when the runs were equal (zarrs_validate.rs:147). */
 int zt_compare_finish(zt_ctx* ctx, const void* state, uint64_t* n_diff, int64_t* first);
 
+/* ---- chunk occupancy (zarrs `store_empty_chunks = false`; Zarr V3 sharding specification) ----- */
+
+/* Which cells of a box hold anything but the fill value. zarrs' `store_empty_chunks` option
+ * (default false) makes Array::store_chunk erase a chunk whose elements all equal the fill value
+ * (FillValue::equals_all, a comparison of the elements' bytes) instead of writing it, and the
+ * sharding codec leave such an inner chunk out of the shard; the Zarr V3 sharding specification
+ * (sharding_indexed, "Binary shard format") marks it with offset and nbytes of 2^64 - 1 in the
+ * shard index. This is that test for a whole device-resident box at once: `data` is a contiguous
+ * C-order box of `shape` (ndim <= ZT_MAX_DIMS, element alignment) of any of the 13 data types,
+ * tiled from its origin by cells of `cell_shape` (extents >= 1; the last cell of an axis may be
+ * partial, a cell may be larger than the box); `fill_bits` holds the fill value's storage bits,
+ * zero-extended little endian. occupied (device memory, one byte per cell, C order of the cell
+ * grid ceil(shape / cell_shape)) becomes 1 where some element's bits differ from the fill
+ * value's, else 0: a NaN fill matches only its own payload, +0.0 is not -0.0, bool is a byte.
+ * Runs on the context's stream; a box with a zero extent has no cells and launches nothing. */
+int zt_chunk_occupancy_is_compatible(int dtype);
+int zt_chunk_occupancy(zt_ctx* ctx, int dtype, const void* data, const int64_t* shape, int ndim,
+                       const int64_t* cell_shape, uint64_t fill_bits, uint8_t* occupied);
+
 /* ---- Zarr V3 store -> store path (host storage in and out) ----------------------------------
  * The reference's filters read and write Zarr arrays through zarrs (Array::retrieve_array_subset_
  * ndarray / store_array_subset_ndarray, guided_filter.rs:95-110; zarrs_ome.rs:226-232). These
@@ -432,6 +451,25 @@ void zt_store_set_progress_callback(zt_progress_fn fn, void* user);
  * Replaces the reference's per-filter `chunk_limit` argument. */
 int zt_store_set_chunk_limit(int64_t max_chunks);
 
+/* zarrs' `store_empty_chunks` option for the store filters and writes made afterwards FROM THIS
+ * THREAD. 1 (the default here; the reference's default is false) stores every chunk. 0 elides
+ * chunks that hold nothing but the fill value, as the reference's stores do: a cell (a chunk, or
+ * an inner chunk of a shard) is empty when the storage bits of every element inside the array's
+ * shape equal the fill value's; an empty chunk of an unsharded array is not written and an
+ * existing file of it is removed; an empty inner chunk adds no bytes to its shard and both words
+ * of its index entry are 2^64 - 1 (Zarr V3 sharding specification), the other inner chunks stay
+ * contiguous; a shard of empty inner chunks is not written and an existing file is removed. An
+ * elided chunk still is a progress step and adds 0 to bytes_written; zarr.json does not change.
+ * The store filters find the empty cells on the device (zt_chunk_occupancy on every output row
+ * before it is copied out); writes from host data scan on the host. A thread starts with 0
+ * instead of 1 when the environment has ZT_STORE_EMPTY_CHUNKS=0 (worker processes inherit the
+ * setting that way). */
+int zt_store_set_store_empty_chunks(int store_empty_chunks);
+/* The chunks (files: chunks of an unsharded array, shards) and the inner chunks inside the
+ * array's inner-chunk grid (of an unsharded array: its chunks) that the last store filter or
+ * write called from this thread elided. Either pointer may be NULL. */
+int zt_store_last_elided(int64_t* chunks, int64_t* inner_chunks);
+
 /* flags for the store filters */
 #define ZT_STORE_ERASE_OUTPUT_METADATA 1 /* remove OUT/zarr.json first ("not finished" marker,
                                              zarrs_filter.rs:297-300) */
@@ -463,6 +501,15 @@ int zt_store_read_subset(const char* path, const int64_t* start, const int64_t* 
 /* Write a chunk-aligned subset (may end at the array edge) from a C-order host buffer. */
 int zt_store_write_subset(const char* path, const int64_t* start, const int64_t* shape,
                           const void* host_in, int nthreads);
+/* zt_store_write_subset with a map the caller already has (zt_chunk_occupancy of the same data
+ * with the array's inner chunk shape as the cell shape, copied to the host): occupied_host holds
+ * one byte per inner chunk of the subset, C order of ceil(shape / inner chunk shape), 0 = empty.
+ * It is consulted when this thread's store_empty_chunks setting is 0, in place of the host scan;
+ * NULL = decide on the host. The data of a cell whose byte is 0 is not read; host_in may be NULL
+ * when the setting is 0 and the whole map is 0 (the subset's chunk files are removed). */
+int zt_store_write_subset_occupancy(const char* path, const int64_t* start, const int64_t* shape,
+                                    const void* host_in, const uint8_t* occupied_host,
+                                    int nthreads);
 /* Fill an existing array with the SURVEY.md §8(d) synthetic data (kind 0: float32 step+noise,
  * kind 1: uint16 noise), identical to zt_synth_step_noise_f32 / zt_synth_u16. */
 int zt_store_write_synth(const char* path, int kind, uint64_t seed, int nthreads);

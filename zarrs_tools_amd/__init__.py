@@ -13,6 +13,7 @@ from .filter import (  # noqa: E402
     ArraySubset,
     ArraySubsetOverlap,
     Clamp,
+    chunk_occupancy,
     Compare,
     Context,
     Crop,
@@ -53,4 +54,5 @@ __all__ = [
     "synth_step_noise_f32", "synth_u16", "synth_box", "torch_dtype",
     "Histogram", "Range", "combine_histograms", "combine_ranges",
     "Compare", "combine_compares",
+    "chunk_occupancy",
 ]

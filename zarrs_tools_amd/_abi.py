@@ -224,6 +224,11 @@ def lib() -> ctypes.CDLL:
         "zt_store_compare": ([ctypes.c_char_p, ctypes.c_char_p, c_int, ctypes.c_int64,
                               ctypes.c_int64, c_int, u64p, ctypes.POINTER(ctypes.c_int64),
                               ctypes.POINTER(StoreStats)], c_int),
+        "zt_chunk_occupancy_is_compatible": ([c_int], c_int),
+        "zt_chunk_occupancy": ([vp, c_int, vp, i64p, c_int, i64p, ctypes.c_uint64, vp], c_int),
+        "zt_store_set_store_empty_chunks": ([c_int], c_int),
+        "zt_store_last_elided": ([i64p, i64p], c_int),
+        "zt_store_write_subset_occupancy": ([ctypes.c_char_p, i64p, i64p, vp, vp, c_int], c_int),
         "zt_synth_step_noise_f32": ([vp, vp, i64p, c_int, i64p, ctypes.c_int64, ctypes.c_uint64],
                                     c_int),
         "zt_synth_u16": ([vp, vp, i64p, c_int, i64p, ctypes.c_int64, ctypes.c_uint64], c_int),

@@ -555,6 +555,36 @@ uint64_t host_available_bytes() {
 // most this many chunks concurrently. Per calling thread; 0 = bounded by memory only.
 thread_local int64_t g_chunk_limit = 0;
 
+// zarrs' store_empty_chunks option (zt_store_set_store_empty_chunks) and what the last store call
+// elided (zt_store_last_elided). Per calling thread.
+// ZT_STORE_EMPTY_CHUNKS=0 in the environment makes "elide" the setting a thread starts with: how
+// the worker processes of a multi-GPU run inherit it.
+int store_empty_chunks_default() {
+    const char* e = std::getenv("ZT_STORE_EMPTY_CHUNKS");
+    return !(e && e[0] == '0' && e[1] == '\0');
+}
+thread_local int g_store_empty_chunks = store_empty_chunks_default();
+thread_local int64_t g_last_elided[2] = {0, 0};
+
+std::vector<int64_t> cell_shape_of(const Array& a) {
+    return a.codecs.sharded ? a.codecs.inner_shape : a.chunk_shape;
+}
+
+// The cells of chunk `idx` in a map over the inner-chunk grid of a chunk-aligned region that
+// starts at array coordinate `origin` and has `mg` cells per axis (C order).
+void occupancy_view(const Array& a, const int64_t* idx, const int64_t* origin,
+                    const std::vector<int64_t>& mg, const uint8_t* map, zt::zarr::Elide& el) {
+    const std::vector<int64_t> cell = cell_shape_of(a), st = c_strides(mg);
+    int64_t off = 0;
+    for (int d = 0; d < a.ndim(); ++d) {
+        const int64_t first = (idx[d] * a.chunk_shape[d] - origin[d]) / cell[d];
+        el.strides[d] = st[d];
+        el.extent[d] = std::min(a.chunk_shape[d] / cell[d], mg[d] - first);
+        off += first * st[d];
+    }
+    el.flags = map + off;
+}
+
 uint64_t device_available_bytes() {
     if (const char* e = std::getenv("ZT_STORE_DEVICE_MEMORY")) return std::strtoull(e, nullptr, 10);
     size_t fr = 0, tot = 0;
@@ -590,6 +620,8 @@ void run_pipeline(const Array& in, const Array& out, int device, int64_t row_beg
                   const ColWin* cw = nullptr) {
     const auto t_start = Clock::now();
     const int nd = in.ndim();
+    const bool elide = g_store_empty_chunks == 0;  // store_empty_chunks = false
+    g_last_elided[0] = g_last_elided[1] = 0;
     const int64_t in_cz = in.chunk_shape[0], out_cz = out.chunk_shape[0];
     const int64_t nz_in = in.shape[0], nz_out = out.shape[0];
     const int64_t out_rows = (nz_out + out_cz - 1) / out_cz;
@@ -681,6 +713,32 @@ void run_pipeline(const Array& in, const Array& out, int device, int64_t row_beg
         dout[s].alloc((size_t)out_cz * out_pb);
     }
 
+    // store_empty_chunks = false: a map of every output row's inner chunks, made on the device
+    // before the row is copied out (zt_chunk_occupancy) and handed to the row's encoders
+    const std::vector<int64_t> occ_cell = cell_shape_of(out);
+    uint64_t fill_bits = 0;
+    std::memcpy(&fill_bits, out.fill.data(), out.esz);  // zero-extended (little-endian host)
+    auto occ_grid = [&](int64_t planes) {  // the cells of a row of `planes` planes, per axis
+        std::vector<int64_t> mg(out.ndim());
+        for (int d = 0; d < out.ndim(); ++d) {
+            const int64_t e = d == 0 ? planes : (cw && d == 1) ? cw->o1 - cw->o0 : out.shape[d];
+            mg[d] = (e + occ_cell[d] - 1) / occ_cell[d];
+        }
+        return mg;
+    };
+    auto occ_cells = [&](int64_t planes) {
+        int64_t n = 1;
+        for (auto g : occ_grid(planes)) n *= g;
+        return n;
+    };
+    DevBuf docc[2];
+    Pinned hocc[2];
+    for (int s = 0; elide && s < NB; ++s) {
+        docc[s].alloc((size_t)occ_cells(out_cz));
+        hocc[s].alloc((size_t)occ_cells(out_cz));
+    }
+    std::atomic<int64_t> elided_chunks{0}, elided_inner{0};
+
     Pool pool(threads);
     std::vector<Group> dec_group(NR);
     Group enc_group[2];
@@ -726,14 +784,22 @@ void run_pipeline(const Array& in, const Array& out, int device, int64_t row_beg
     auto submit_encode = [&](int64_t k) {
         const int s = (int)(k % NB);
         uint8_t* buf = hout[s].u8();
+        const uint8_t* map = hocc[s].u8();
+        const std::vector<int64_t> mg =
+            elide ? occ_grid(std::min((k + 1) * out_cz, nz_out) - k * out_cz)
+                  : std::vector<int64_t>();
         for (auto& idx : chunks_in_rows(out, k, k + 1, oc0, oc1)) {
-            pool.submit(enc_group[s], [&, idx, buf, k] {
+            pool.submit(enc_group[s], [&, idx, buf, k, map, mg] {
                 const auto t0 = Clock::now();
                 std::vector<int64_t> origin(out.ndim(), 0);
                 origin[0] = k * out_cz;
                 if (cw) origin[1] = cw->o0;
+                zt::zarr::Elide el;
+                if (elide) occupancy_view(out, idx.data(), origin.data(), mg, map, el);
                 size_t n = out.write_chunk(idx.data(), buf, origin.data(), out_row_shape.data(),
-                                           out_row_st.data());
+                                           out_row_st.data(), elide ? &el : nullptr);
+                elided_chunks += el.chunks;
+                elided_inner += el.inner_chunks;
                 bytes_written += n;
                 enc_ns += (int64_t)(secs_since(t0) * 1e9);
                 std::lock_guard<std::mutex> lk(g_progress_mu);
@@ -808,12 +874,23 @@ void run_pipeline(const Array& in, const Array& out, int device, int64_t row_beg
             const int64_t z0 = k * out_cz, z1 = std::min(z0 + out_cz, nz_out);
             if (int rc = op.apply(ctx.c, dslab[s].p, in0, in1, dout[s].p, z0, z1))
                 throw zt::zarr::Error(rc, zt_last_error());
+            if (elide) {  // the row's real extents, cells of the inner chunk shape
+                std::vector<int64_t> ext(out_row_shape);
+                ext[0] = z1 - z0;
+                if (int rc = zt_chunk_occupancy(ctx.c, out.dtype, dout[s].p, ext.data(),
+                                                out.ndim(), occ_cell.data(), fill_bits,
+                                                docc[s].u8()))
+                    throw zt::zarr::Error(rc, zt_last_error());
+            }
             HIPCHK(hipEventRecord(ev_k[s], s_comp));
             // D2H
             HIPCHK(hipStreamWaitEvent(s_d2h, ev_k[s], 0));
             HIPCHK(hipEventRecord(ev_d2h0[s], s_d2h));
             HIPCHK(hipMemcpyAsync(hout[s].u8(), dout[s].p, (size_t)(z1 - z0) * out_pb,
                                   hipMemcpyDeviceToHost, s_d2h));
+            if (elide)
+                HIPCHK(hipMemcpyAsync(hocc[s].p, docc[s].p, (size_t)occ_cells(z1 - z0),
+                                      hipMemcpyDeviceToHost, s_d2h));
             HIPCHK(hipEventRecord(ev_d2h[s], s_d2h));
             if (pending_enc >= 0) finish_row(pending_enc);
             pending_enc = k;
@@ -829,6 +906,8 @@ void run_pipeline(const Array& in, const Array& out, int device, int64_t row_beg
         (void)hipDeviceSynchronize();
         throw;
     }
+    g_last_elided[0] = elided_chunks.load();
+    g_last_elided[1] = elided_inner.load();
     if (st) {
         st->wall_s = secs_since(t_start);
         st->decode_s = dec_ns.load() * 1e-9;
@@ -1252,12 +1331,30 @@ int zt_store_read_subset(const char* path, const int64_t* start, const int64_t* 
 
 int zt_store_write_subset(const char* path, const int64_t* start, const int64_t* shape,
                           const void* host_in, int nthreads) {
+    return zt_store_write_subset_occupancy(path, start, shape, host_in, nullptr, nthreads);
+}
+
+int zt_store_write_subset_occupancy(const char* path, const int64_t* start, const int64_t* shape,
+                                    const void* host_in, const uint8_t* occupied_host,
+                                    int nthreads) {
     try {
-        if (!path || !start || !shape || !host_in)
+        const bool elide = g_store_empty_chunks == 0;
+        g_last_elided[0] = g_last_elided[1] = 0;
+        if (!path || !start || !shape)
             return zt::set_last_error(ZT_ERR_INVALID_PARAMETERS, "null argument");
         Array a = Array::open(path);
         const int nd = a.ndim();
         std::vector<int64_t> st(start, start + nd), sh(shape, shape + nd);
+        if (!host_in) {  // no data: only for a subset the caller's map declares empty
+            bool ok = elide && occupied_host;
+            const std::vector<int64_t> cs = cell_shape_of(a);
+            int64_t cells = 1;
+            for (int d = 0; d < nd; ++d) cells *= sh[d] > 0 ? (sh[d] + cs[d] - 1) / cs[d] : 0;
+            for (int64_t i = 0; ok && i < cells; ++i) ok = occupied_host[i] == 0;
+            if (!ok)
+                return zt::set_last_error(ZT_ERR_INVALID_PARAMETERS,
+                                          "null data: only with elision on and an all-zero map");
+        }
         std::vector<int64_t> c0(nd), c1(nd);
         int64_t n = 1;
         for (int d = 0; d < nd; ++d) {
@@ -1273,6 +1370,11 @@ int zt_store_write_subset(const char* path, const int64_t* start, const int64_t*
             n *= c1[d] - c0[d];
         }
         const auto strides = c_strides(sh);
+        // the subset's inner-chunk grid (the caller's map, if any, is laid out over it)
+        const std::vector<int64_t> cell = cell_shape_of(a);
+        std::vector<int64_t> mg(nd);
+        for (int d = 0; d < nd; ++d) mg[d] = (sh[d] + cell[d] - 1) / cell[d];
+        std::atomic<int64_t> elided_chunks{0}, elided_inner{0};
         Pool pool(resolve_threads(nthreads));
         Group g;
         const uint8_t* src = static_cast<const uint8_t*>(host_in);
@@ -1283,9 +1385,19 @@ int zt_store_write_subset(const char* path, const int64_t* start, const int64_t*
                 idx[d] = c0[d] + rem % (c1[d] - c0[d]);
                 rem /= c1[d] - c0[d];
             }
-            pool.submit(g, [&, idx] { a.write_chunk(idx.data(), src, st.data(), sh.data(), strides.data()); });
+            pool.submit(g, [&, idx] {
+                zt::zarr::Elide el;
+                if (elide && occupied_host)
+                    occupancy_view(a, idx.data(), st.data(), mg, occupied_host, el);
+                a.write_chunk(idx.data(), src, st.data(), sh.data(), strides.data(),
+                              elide ? &el : nullptr);
+                elided_chunks += el.chunks;
+                elided_inner += el.inner_chunks;
+            });
         }
         g.wait();
+        g_last_elided[0] = elided_chunks.load();
+        g_last_elided[1] = elided_inner.load();
         return ZT_OK;
     } catch (const std::exception& e) {
         return report(e);
@@ -1306,6 +1418,9 @@ int zt_store_write_synth(const char* path, int kind, uint64_t seed, int nthreads
         for (auto x : g) n *= x;
         const auto astr = c_strides(a.shape);
         const int64_t nx = a.shape[nd - 1];
+        const bool elide = g_store_empty_chunks == 0;
+        g_last_elided[0] = g_last_elided[1] = 0;
+        std::atomic<int64_t> elided_chunks{0}, elided_inner{0};
         Pool pool(resolve_threads(nthreads));
         Group grp;
         for (int64_t c = 0; c < n; ++c) {
@@ -1341,10 +1456,16 @@ int zt_store_write_synth(const char* path, int kind, uint64_t seed, int nthreads
                         std::memcpy(&buf[(size_t)i * 2], &v, 2);
                     }
                 }
-                a.write_chunk(idx.data(), buf.data(), org.data(), box.data(), bst.data());
+                zt::zarr::Elide el;  // no map: the host scan decides
+                a.write_chunk(idx.data(), buf.data(), org.data(), box.data(), bst.data(),
+                              elide ? &el : nullptr);
+                elided_chunks += el.chunks;
+                elided_inner += el.inner_chunks;
             });
         }
         grp.wait();
+        g_last_elided[0] = elided_chunks.load();
+        g_last_elided[1] = elided_inner.load();
         return ZT_OK;
     } catch (const std::exception& e) {
         return report(e);
@@ -1807,6 +1928,17 @@ void zt_store_set_progress_callback(zt_progress_fn fn, void* user) {
 int zt_store_set_chunk_limit(int64_t max_chunks) {
     if (max_chunks < 0) return zt::set_last_error(ZT_ERR_INVALID_PARAMETERS, "chunk limit must be >= 0");
     g_chunk_limit = max_chunks;
+    return ZT_OK;
+}
+
+int zt_store_set_store_empty_chunks(int store_empty_chunks) {
+    g_store_empty_chunks = store_empty_chunks ? 1 : 0;
+    return ZT_OK;
+}
+
+int zt_store_last_elided(int64_t* chunks, int64_t* inner_chunks) {
+    if (chunks) *chunks = g_last_elided[0];
+    if (inner_chunks) *inner_chunks = g_last_elided[1];
     return ZT_OK;
 }
 

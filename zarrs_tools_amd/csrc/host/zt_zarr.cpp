@@ -499,7 +499,8 @@ std::vector<uint8_t> CodecChain::decode_bytes(const std::vector<uint8_t>& bytes,
 }
 
 std::vector<uint8_t> CodecChain::encode(const uint8_t* raw, const std::vector<int64_t>& shape,
-                                        size_t esz, const uint8_t* fill) const {
+                                        size_t esz, const uint8_t* fill, Elide* el,
+                                        const int64_t* in_array) const {
     const int nd = (int)shape.size();
     if (!sharded) return encode_bytes(std::vector<uint8_t>(raw, raw + prod(shape) * esz), esz);
     // Shard: inner chunks in C order of the inner grid, then the (offset, nbytes) index.
@@ -511,14 +512,36 @@ std::vector<uint8_t> CodecChain::encode(const uint8_t* raw, const std::vector<in
     std::vector<uint64_t> idx((size_t)n_inner * 2);
     std::vector<uint8_t> body, tmp((size_t)ie * esz);
     std::vector<int64_t> box(nd);
+    int64_t n_stored = 0;
     for (int64_t c = 0; c < n_inner; ++c) {
-        int64_t rem = c, off = 0;
+        int64_t rem = c, off = 0, foff = 0;
+        bool inside = true;  // the inner chunk meets the array (it has a flag)
         for (int d = nd - 1; d >= 0; --d) {
             int64_t ci = rem % ig[d];
             rem /= ig[d];
             off += ci * inner_shape[d] * sst[d];
             box[d] = std::min(inner_shape[d], shape[d] - ci * inner_shape[d]);
+            if (el) {
+                const int64_t have = el->flags ? el->extent[d]
+                                     : in_array ? (in_array[d] + inner_shape[d] - 1) / inner_shape[d]
+                                                : ig[d];
+                inside = inside && ci < have;
+                foff += ci * el->strides[d];
+            }
         }
+        if (el) {
+            // the chunk's padding holds the fill value, so a scan of the whole inner chunk is a
+            // scan of its elements inside the array
+            const bool empty = !inside || (el->flags ? el->flags[foff] == 0
+                                                     : box_is_fill(raw + off * esz, sst.data(),
+                                                                   box.data(), nd, esz, fill));
+            if (empty) {
+                idx[2 * c] = idx[2 * c + 1] = ~0ULL;
+                if (inside) ++el->inner_chunks;
+                continue;
+            }
+        }
+        ++n_stored;
         fill_elems(tmp.data(), (size_t)ie, fill, esz);
         copy_box(raw + off * esz, sst.data(), tmp.data(), ist.data(), box.data(), nd, esz);
         std::vector<uint8_t> enc = inner->encode(tmp.data(), inner_shape, esz, fill);
@@ -528,10 +551,12 @@ std::vector<uint8_t> CodecChain::encode(const uint8_t* raw, const std::vector<in
     }
     std::vector<uint8_t> ib((size_t)n_inner * 16);
     std::memcpy(ib.data(), idx.data(), ib.size());  // little-endian host
+    if (el && n_stored == 0) return {};  // nothing but the fill value: no shard
     if (!index_at_end) {
         // offsets are relative to the shard start: shift by the encoded index size
         std::vector<uint8_t> probe = index->encode_bytes(ib, 8);
-        for (int64_t c = 0; c < n_inner; ++c) idx[2 * c] += probe.size();
+        for (int64_t c = 0; c < n_inner; ++c)
+            if (idx[2 * c + 1] != ~0ULL) idx[2 * c] += probe.size();
         std::memcpy(ib.data(), idx.data(), ib.size());
     }
     std::vector<uint8_t> ienc = index->encode_bytes(ib, 8);
@@ -591,7 +616,37 @@ void CodecChain::decode(const std::vector<uint8_t>& bytes, uint8_t* raw,
     }
 }
 
-// ---- strided box copy --------------------------------------------------------------------------
+// ---- strided box copy and scan -----------------------------------------------------------------
+
+bool box_is_fill(const uint8_t* src, const int64_t* ss, const int64_t* box, int nd, size_t esz,
+                 const uint8_t* fill) {
+    for (int d = 0; d < nd; ++d)
+        if (box[d] <= 0) return true;
+    const int64_t run = box[nd - 1];
+    int64_t outer = 1;
+    for (int d = 0; d < nd - 1; ++d) outer *= box[d];
+    // the fill pattern of one run when the run is contiguous
+    std::vector<uint8_t> pat;
+    if (ss[nd - 1] == 1) {
+        pat.resize((size_t)run * esz);
+        fill_elems(pat.data(), (size_t)run, fill, esz);
+    }
+    for (int64_t o = 0; o < outer; ++o) {
+        int64_t rem = o, so = 0;
+        for (int d = nd - 2; d >= 0; --d) {
+            so += (rem % box[d]) * ss[d];
+            rem /= box[d];
+        }
+        if (!pat.empty()) {
+            if (std::memcmp(src + so * esz, pat.data(), pat.size()) != 0) return false;
+        } else {
+            for (int64_t i = 0; i < run; ++i)
+                if (std::memcmp(src + (so + i * ss[nd - 1]) * esz, fill, esz) != 0) return false;
+        }
+    }
+    return true;
+}
+
 
 void copy_box(const uint8_t* src, const int64_t* ss, uint8_t* dst, const int64_t* ds,
               const int64_t* box, int nd, size_t esz) {
@@ -838,7 +893,7 @@ size_t Array::read_chunk(const int64_t* idx, uint8_t* dst, const int64_t* dst_or
 }
 
 size_t Array::write_chunk(const int64_t* idx, const uint8_t* src, const int64_t* src_origin,
-                          const int64_t* src_shape, const int64_t* src_strides) const {
+                          const int64_t* src_shape, const int64_t* src_strides, Elide* el) const {
     const int nd = ndim();
     std::vector<int64_t> lo(nd), box(nd), cst(nd);
     bool full = true;
@@ -854,6 +909,34 @@ size_t Array::write_chunk(const int64_t* idx, const uint8_t* src, const int64_t*
     c_strides(chunk_shape, cst.data());
     int64_t soff = 0;
     for (int d = 0; d < nd; ++d) soff += (lo[d] - src_origin[d]) * src_strides[d];
+    // store_empty_chunks = false: no file for a chunk that holds nothing but the fill value, and
+    // none left over from an earlier write (zarrs' store_chunk erases it)
+    auto erase = [&] {
+        const std::string p = chunk_path(idx);
+        if (::unlink(p.c_str()) != 0 && errno != ENOENT)
+            raise(ZT_ERR_IO, "remove " + p + ": " + std::strerror(errno));
+        ++el->chunks;
+        return (size_t)0;
+    };
+    if (el && !codecs.sharded) {
+        const bool empty = el->flags ? el->flags[0] == 0
+                                     : box_is_fill(src + soff * esz, src_strides, box.data(), nd,
+                                                   esz, fill.data());
+        if (empty) {
+            ++el->inner_chunks;
+            return erase();
+        }
+    }
+    if (el && codecs.sharded && el->flags) {  // a shard the map knows to be empty: no copy at all
+        std::vector<int64_t> ext(el->extent, el->extent + nd);
+        const uint8_t zero = 0;
+        if (box_is_fill(el->flags, el->strides, ext.data(), nd, 1, &zero)) {
+            int64_t cells = 1;
+            for (int d = 0; d < nd; ++d) cells *= ext[d];
+            el->inner_chunks += cells;
+            return erase();
+        }
+    }
     const bool raw_codec = !codecs.sharded && codecs.b2b.empty() && !codecs.big_endian;
     if (raw_codec && full && src_strides[nd - 1] == 1) {
         // uncompressed full chunk: gather the runs of the source straight into the file
@@ -880,7 +963,9 @@ size_t Array::write_chunk(const int64_t* idx, const uint8_t* src, const int64_t*
     std::vector<uint8_t> enc =
         (!codecs.sharded && codecs.b2b.empty() && !codecs.big_endian)
             ? std::move(raw)
-            : codecs.encode(raw.data(), chunk_shape, esz, fill.data());
+            : codecs.encode(raw.data(), chunk_shape, esz, fill.data(),
+                            codecs.sharded ? el : nullptr, box.data());
+    if (el && codecs.sharded && enc.empty()) return erase();
     write_file(chunk_path(idx), enc.data(), enc.size());
     return enc.size();
 }

@@ -45,6 +45,20 @@ struct BytesCodec {
     json::Value to_json() const;
 };
 
+// zarrs' `store_empty_chunks = false` for one chunk being written. A cell (the chunk of an
+// unsharded array, an inner chunk of a shard) is empty when every element of it inside the
+// array's shape has the fill value's bytes (FillValue::equals_all). `flags` (optional) holds what
+// the caller already knows, one byte per cell of the chunk that lies inside the array's
+// inner-chunk grid (0 = empty): cell (i0, i1, ..) of the chunk is flags[sum i_d * strides[d]] for
+// i_d < extent[d]; cells beyond `extent` are padding of an edge shard, which is empty. Without
+// flags the data is compared with the fill value on the host. The counts are added to.
+struct Elide {
+    const uint8_t* flags = nullptr;
+    int64_t strides[8] = {0}, extent[8] = {0};
+    int64_t chunks = 0;        // chunks (files) not written
+    int64_t inner_chunks = 0;  // empty cells inside the array's inner-chunk grid
+};
+
 // A codec chain: [bytes | sharding_indexed] followed by bytes -> bytes codecs.
 struct CodecChain {
     bool big_endian = false;
@@ -58,8 +72,13 @@ struct CodecChain {
     static CodecChain from_json(const json::Value& codecs, int ndim);
     json::Value to_json() const;
     // Encode / decode one chunk of `shape` (C order, `esz`-byte elements).
+    // With `el` (sharded chains): empty inner chunks add no bytes and get the index entry
+    // (2^64 - 1, 2^64 - 1) of the Zarr V3 sharding specification; the result is empty when every
+    // inner chunk is (the shard is not to be written). `in_array`: the extents of the chunk that
+    // lie inside the array (what counts as inside the inner-chunk grid when el has no flags).
     std::vector<uint8_t> encode(const uint8_t* raw, const std::vector<int64_t>& shape, size_t esz,
-                                const uint8_t* fill) const;
+                                const uint8_t* fill, Elide* el = nullptr,
+                                const int64_t* in_array = nullptr) const;
     // Decodes into `raw` (shape elements). Returns false if the chunk is absent in a shard.
     void decode(const std::vector<uint8_t>& bytes, uint8_t* raw,
                 const std::vector<int64_t>& shape, size_t esz, const uint8_t* fill) const;
@@ -104,8 +123,11 @@ class Array {
                       const int64_t* dst_shape, const int64_t* dst_strides) const;
     // Encode chunk `idx` from the same kind of region (must cover the chunk's in-array part);
     // elements beyond the array edge are written as the fill value. Returns bytes written.
+    // With `el`: a chunk without an occupied cell is not written, an existing file of it is removed
+    // and 0 is returned; a shard leaves its empty inner chunks out.
     size_t write_chunk(const int64_t* idx, const uint8_t* src, const int64_t* src_origin,
-                       const int64_t* src_shape, const int64_t* src_strides) const;
+                       const int64_t* src_shape, const int64_t* src_strides,
+                       Elide* el = nullptr) const;
 };
 
 // Fill-value JSON for a dtype from a double (NaN/Infinity as strings), and the element bytes of a
@@ -117,6 +139,10 @@ std::vector<uint8_t> fill_bytes(int dtype, const json::Value& v);
 // Strided copy of an n-D box between two C-order buffers (element size esz).
 void copy_box(const uint8_t* src, const int64_t* src_strides, uint8_t* dst,
               const int64_t* dst_strides, const int64_t* box, int ndim, size_t esz);
+
+// Every element of the box has the bytes of `fill` (memcmp against the fill pattern, run by run).
+bool box_is_fill(const uint8_t* src, const int64_t* src_strides, const int64_t* box, int ndim,
+                 size_t esz, const uint8_t* fill);
 
 uint32_t crc32c(const uint8_t* p, size_t n);
 bool zstd_available();

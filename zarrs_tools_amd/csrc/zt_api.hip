@@ -1488,6 +1488,40 @@ int zt_compare_finish(zt_ctx* ctx, const void* state, uint64_t* n_diff, int64_t*
     return ZT_OK;
 }
 
+// ---- chunk occupancy (zarrs store_empty_chunks = false) -----------------------------------------
+
+int zt_chunk_occupancy_is_compatible(int dtype) {
+    if (!valid_dtype(dtype))
+        return fail(ZT_ERR_UNSUPPORTED_DATA_TYPE, "Unsupported data type code %d", dtype);
+    return ZT_OK;
+}
+
+int zt_chunk_occupancy(zt_ctx* ctx, int dtype, const void* data, const int64_t* shape, int ndim,
+                       const int64_t* cell_shape, uint64_t fill_bits, uint8_t* occupied) {
+    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = zt_chunk_occupancy_is_compatible(dtype)) return rc;
+    if (!shape || !cell_shape || ndim < 1 || ndim > ZT_MAX_DIMS)
+        return fail(ZT_ERR_INVALID_PARAMETERS, "shape / cell_shape of 1 to %d axes", ZT_MAX_DIMS);
+    int64_t n = 1;
+    for (int d = 0; d < ndim; ++d) {
+        if (shape[d] < 0) return fail(ZT_ERR_INVALID_PARAMETERS, "negative extent");
+        if (cell_shape[d] < 1) return fail(ZT_ERR_INVALID_PARAMETERS, "cell extents must be >= 1");
+        if (shape[d] > 0 && n > INT64_MAX / 16 / shape[d])
+            return fail(ZT_ERR_INVALID_PARAMETERS, "the box is too large");
+        n *= shape[d];
+    }
+    if (n == 0) return ZT_OK;
+    if (int rc = info_run_ok(dtype, data, n)) return rc;
+    if (!occupied) return fail(ZT_ERR_INVALID_PARAMETERS, "null pointer");
+    DeviceGuard guard(ctx->device);
+    if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev0, ctx->cur));
+    hipError_t e = zt::launch_chunk_occupancy(data, (int)zt::dtype_size(dtype), shape, ndim,
+                                              cell_shape, fill_bits, occupied, ctx->cur);
+    if (e != hipSuccess) return hip_fail(e, "chunk occupancy launch");
+    if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev1, ctx->cur));
+    return ZT_OK;
+}
+
 // ---- downsample ------------------------------------------------------------------------------
 
 int zt_downsample_is_compatible(int dtype_in, int dtype_out, int discrete) {

@@ -223,6 +223,16 @@ hipError_t launch_compare_init(void* state, hipStream_t s);
 hipError_t launch_compare_accumulate(const void* a, const void* b, int esz, int64_t n,
                                      int64_t base, void* state, hipStream_t s);
 
+// Chunk occupancy (occupancy.hip; zarrs' `store_empty_chunks = false`, FillValue::equals_all): a
+// contiguous C-order box of `shape` (ndim <= kMaxDims) elements of `esz` bytes (1, 2, 4 or 8) at
+// element alignment, tiled from its origin by cells of `cell_shape` (the last cell of an axis may
+// be partial). occupied[c] (device, one byte per cell, C order of the cell grid) becomes 1 when
+// some element of cell c differs bitwise from the low `esz` bytes of fill_bits, else 0; the flags
+// are cleared on `s` first. A box with a zero extent has no cells: nothing is launched.
+hipError_t launch_chunk_occupancy(const void* data, int esz, const int64_t* shape, int ndim,
+                                  const int64_t* cell_shape, uint64_t fill_bits, uint8_t* occupied,
+                                  hipStream_t s);
+
 // Synthetic inputs
 hipError_t launch_synth_step_noise_f32(float* out, int64_t n, int64_t plane, int64_t nx_row,
                                        int64_t nx_global, int64_t z0, uint64_t seed,

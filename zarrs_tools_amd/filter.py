@@ -19,6 +19,8 @@ Names, argument meaning and error behaviour follow LDeakin/zarrs_tools 0.7.2:
     reductions; ``combine_ranges`` / ``combine_histograms`` join partial results)
   - ``Compare`` <- src/bin/zarrs_validate.rs:145-147 (the bitwise comparison of two arrays;
     ``combine_compares`` joins partial results)
+  - ``chunk_occupancy`` <- zarrs' ``store_empty_chunks = false`` (which chunks of a device
+    array hold anything but the fill value)
   - ``ArraySubsetOverlap`` <- src/filter/array_subset_overlap.rs:4-52
 Arrays are device-resident torch tensors (torch is used only for device memory and streams);
 every computation runs in libzarrs_tools_amd.so through the C ABI.
@@ -93,6 +95,10 @@ class Context:
         ms = ctypes.c_float()
         check(lib().zt_ctx_last_kernel_ms(self._h, ctypes.byref(ms)))
         return float(ms.value)
+
+    def chunk_occupancy(self, x, cell_shape=None, fill_value=0):
+        """chunk_occupancy(x, cell_shape, fill_value) on this context."""
+        return chunk_occupancy(x, cell_shape, fill_value, ctx=self)
 
     def close(self) -> None:
         if self._h:
@@ -173,6 +179,11 @@ class DeviceArray:
 
     def chunk_grid_shape(self):
         return tuple(-(-s // c) for s, c in zip(self.shape, self.chunk_shape))
+
+    def chunk_occupancy(self, fill_value=0, cell_shape=None, ctx=None):
+        """Which chunks (or cells of `cell_shape`) hold anything but `fill_value`
+        (chunk_occupancy)."""
+        return chunk_occupancy(self, cell_shape, fill_value, ctx=ctx)
 
     def chunk_subset_bounded(self, chunk_indices) -> ArraySubset:
         start = tuple(i * c for i, c in zip(chunk_indices, self.chunk_shape))
@@ -980,6 +991,44 @@ class Histogram:
         hist = self.new_state(x.device)
         self.accumulate(v, hist, ctx)
         return self.finish(hist)
+
+
+def fill_value_bits(fill_value, dtype: str) -> int:
+    """The storage bits (zero-extended) of a fill value of `dtype`: a Zarr V3 fill_value (a JSON
+    number, true / false, "NaN", "Infinity", "-Infinity", or the raw bits as "0x..." for a float
+    type), read as element_bits reads a value."""
+    if isinstance(fill_value, str) and fill_value[:2] in ("0x", "0X"):
+        if dtype not in DTYPES:
+            raise _abi.UnsupportedDataType(_abi.ERR_UNSUPPORTED_DATA_TYPE,
+                                           f"Unsupported data type {dtype}")
+        size = lib().zt_dtype_size(DTYPES[dtype])
+        return int(fill_value, 16) & ((1 << (8 * size)) - 1)
+    return element_bits(fill_value, dtype)
+
+
+def chunk_occupancy(x, cell_shape: Optional[Sequence[int]] = None, fill_value=0,
+                    ctx: Optional[Context] = None):
+    """Which cells of a device tensor (or DeviceArray, whose chunk shape is the default cell
+    shape) hold anything but the fill value: a uint8 device tensor of shape ceil(shape /
+    cell_shape), 1 = some element's storage bits differ from the fill value's
+    (zt_chunk_occupancy; what zarrs' store_empty_chunks = false tests per chunk). The cells tile
+    the tensor from its origin. `fill_value` as fill_value_bits takes it."""
+    torch = _torch()
+    if isinstance(x, DeviceArray) and cell_shape is None:
+        cell_shape = x.chunk_shape
+    v, dtype = _info_run(x)
+    if cell_shape is None or len(cell_shape) != v.dim():
+        raise _invalid("chunk_occupancy: one cell extent per axis")
+    cell = [int(c) for c in cell_shape]
+    if any(c < 1 for c in cell):
+        raise _invalid("chunk_occupancy: cell extents must be >= 1")
+    bits = fill_value_bits(fill_value, dtype)
+    grid = [-(-int(n) // c) for n, c in zip(v.shape, cell)]
+    occ = torch.empty(grid, dtype=torch.uint8, device=v.device)
+    ctx = ctx or default_context(v.device.index)
+    check(lib().zt_chunk_occupancy(ctx.handle, _info_dtype(dtype), _ptr(v), i64_array(v.shape),
+                                   v.dim(), i64_array(cell), bits, _ptr(occ)))
+    return occ
 
 
 def combine_compares(parts):

@@ -11,6 +11,7 @@ from __future__ import annotations
 import ctypes
 import json
 import os
+import threading
 from dataclasses import dataclass
 from typing import Optional, Sequence
 
@@ -121,13 +122,49 @@ def read_array(path, start=None, shape=None, nthreads: int = 0,
     return out
 
 
-def write_array(path, data: np.ndarray, start=None, nthreads: int = 0) -> None:
-    """Array::store_array_subset_ndarray for a chunk-aligned subset."""
+def write_array(path, data: np.ndarray, start=None, nthreads: int = 0, occupied=None) -> None:
+    """Array::store_array_subset_ndarray for a chunk-aligned subset. `occupied` (used when this
+    thread elides empty chunks, set_store_empty_chunks(False)): what the caller already knows
+    about the data, one byte per inner chunk of the subset in C order of ceil(shape / inner chunk
+    shape), 0 = nothing but the fill value (filter.chunk_occupancy of the same data); None = the
+    data is scanned on the host."""
     info = open_array(path)
     data = np.ascontiguousarray(data)
     start = [0] * info.ndim if start is None else [int(s) for s in start]
-    check(lib().zt_store_write_subset(_b(path), i64_array(start), i64_array(data.shape),
-                                      data.ctypes.data_as(ctypes.c_void_p), int(nthreads)))
+    occ = None
+    if occupied is not None:
+        grid = tuple(-(-int(n) // int(c)) for n, c in zip(data.shape, info.inner_chunk_shape))
+        occ = np.ascontiguousarray(occupied, dtype=np.uint8)
+        if occ.shape != grid:
+            raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS,
+                                         f"write_array: occupied has shape {occ.shape}, the "
+                                         f"subset has {grid} inner chunks")
+    check(lib().zt_store_write_subset_occupancy(
+        _b(path), i64_array(start), i64_array(data.shape), data.ctypes.data_as(ctypes.c_void_p),
+        None if occ is None else occ.ctypes.data_as(ctypes.c_void_p), int(nthreads)))
+
+
+def write_empty(path, start, shape, nthreads: int = 0) -> None:
+    """write_array of a chunk-aligned subset that the caller knows to hold nothing but the fill
+    value, for a thread that elides empty chunks: nothing is written and the subset's chunk files
+    are removed. No data is passed."""
+    info = open_array(path)
+    grid = [-(-int(n) // int(c)) for n, c in zip(shape, info.inner_chunk_shape)]
+    occ = np.zeros(grid, dtype=np.uint8)
+    check(lib().zt_store_write_subset_occupancy(
+        _b(path), i64_array(start), i64_array(shape), None,
+        occ.ctypes.data_as(ctypes.c_void_p), int(nthreads)))
+
+
+def fill_value_of(path):
+    """The fill_value of an array's metadata (also of an array whose metadata is held)."""
+    for name in ("zarr.json", PENDING_METADATA):
+        try:
+            with open(os.path.join(path, name)) as f:
+                return json.load(f)["fill_value"]
+        except FileNotFoundError:
+            continue
+    raise _abi.FilterError(_abi.ERR_STORAGE, f"no Zarr V3 array at {path}")
 
 
 def write_synth(path, kind: int = SYNTH_STEP_NOISE_F32, seed: int = SEED,
@@ -262,6 +299,40 @@ def set_chunk_limit(chunk_limit) -> None:
     check(lib().zt_store_set_chunk_limit(int(chunk_limit or 0)))
 
 
+STORE_EMPTY_CHUNKS_ENV = "ZT_STORE_EMPTY_CHUNKS"  # "0": the default of new threads is to elide
+_store_empty = threading.local()
+
+
+def store_empty_chunks() -> bool:
+    """This thread's setting (set_store_empty_chunks)."""
+    if not hasattr(_store_empty, "v"):
+        _store_empty.v = os.environ.get(STORE_EMPTY_CHUNKS_ENV) != "0"
+    return _store_empty.v
+
+
+def set_store_empty_chunks(store_empty_chunks: bool) -> None:
+    """zarrs' `store_empty_chunks` for the store filters and writes this thread makes next
+    (zt_store_set_store_empty_chunks). True (the default) stores every chunk; False leaves out
+    the chunks, and the inner chunks of shards, that hold nothing but the fill value, and removes
+    the files of chunks that became empty, as the reference's stores do."""
+    check(lib().zt_store_set_store_empty_chunks(int(bool(store_empty_chunks))))
+    _store_empty.v = bool(store_empty_chunks)
+
+
+def last_elided() -> tuple:
+    """(chunks, inner_chunks) that the last store filter or write of this thread elided: chunk
+    files not written, and empty inner chunks inside the array's inner-chunk grid (the chunks
+    themselves for an unsharded array)."""
+    c, i = ctypes.c_int64(), ctypes.c_int64()
+    check(lib().zt_store_last_elided(ctypes.byref(c), ctypes.byref(i)))
+    return c.value, i.value
+
+
+def _stats(st) -> dict:
+    """The stats of a store filter that just ran on this thread."""
+    return {**st.as_dict(), "chunks_elided": last_elided()[0]}
+
+
 def _flags(erase: bool, finish: bool) -> int:
     return (_abi.STORE_ERASE_OUTPUT_METADATA if erase else 0) | (
         _abi.STORE_FINISH_OUTPUT if finish else 0)
@@ -284,7 +355,7 @@ def guided_filter(input_path, output_path, epsilon: float, radius: int,
                                            _enc(encoding), float(epsilon), int(radius),
                                            int(device), r0, r1, c0, c1, int(nthreads),
                                            _flags(erase, finish), ctypes.byref(st)))
-    return st.as_dict()
+    return _stats(st)
 
 
 def downsample(input_path, output_path, stride, discrete: bool = False,
@@ -299,7 +370,7 @@ def downsample(input_path, output_path, stride, discrete: bool = False,
                                     int(bool(discrete)), _dt(data_type), _enc(encoding),
                                     int(device), r0, r1,
                                     int(nthreads), _flags(erase, finish), ctypes.byref(st)))
-    return st.as_dict()
+    return _stats(st)
 
 
 def _sigma_half(sigma, kernel_half_size):
@@ -320,7 +391,7 @@ def gaussian(input_path, output_path, sigma, kernel_half_size, data_type: Option
                                   _enc(encoding), sg, hs,
                                   int(device), r0, r1, int(nthreads), _flags(erase, finish),
                                   ctypes.byref(st)))
-    return st.as_dict()
+    return _stats(st)
 
 
 def gradient_magnitude(input_path, output_path, operator: str = "sobel",
@@ -338,7 +409,7 @@ def gradient_magnitude(input_path, output_path, operator: str = "sobel",
                                             _enc(encoding), op, int(device), r0, r1,
                                             int(nthreads), _flags(erase, finish),
                                             ctypes.byref(st)))
-    return st.as_dict()
+    return _stats(st)
 
 
 def summed_area_table(input_path, output_path, data_type: Optional[str] = None, device: int = 0,
@@ -352,7 +423,7 @@ def summed_area_table(input_path, output_path, data_type: Optional[str] = None, 
     check(lib().zt_store_summed_area_table(_b(input_path), _b(output_path), _dt(data_type),
                                            _enc(encoding), int(device), int(nthreads),
                                            _flags(erase, finish), ctypes.byref(st)))
-    return st.as_dict()
+    return _stats(st)
 
 
 def pointwise_output(filt, input_data_type: str, data_type: Optional[str] = None, encoding=None):
@@ -389,7 +460,7 @@ def pointwise(input_path, output_path, filters, dtypes_out, device: int = 0, row
                                    _enc(encoding), prog.ops, prog.n_ops, off, shp, int(device),
                                    r0, r1, int(nthreads), _flags(erase, finish),
                                    ctypes.byref(st)))
-    return st.as_dict()
+    return _stats(st)
 
 
 def _pointwise_one(filt, input_path, output_path, data_type, encoding, **kw) -> dict:
@@ -537,4 +608,4 @@ def downsample_gaussian(input_path, output_path, stride, sigma, kernel_half_size
                                              int(device), r0, r1,
                                              int(nthreads), _flags(erase, finish),
                                              ctypes.byref(st)))
-    return st.as_dict()
+    return _stats(st)

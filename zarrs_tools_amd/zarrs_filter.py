@@ -111,6 +111,11 @@ def _parse_fill_value(s: str):
         return s
 
 
+SKIP_EMPTY_HELP = ("do not store chunks (or inner chunks of shards) that hold nothing but the "
+                   "fill value, and remove such chunks of an output being overwritten (zarrs' "
+                   "store_empty_chunks = false)")
+
+
 def _add_reencode_args(p: argparse.ArgumentParser) -> None:
     p.add_argument("-d", "--data-type", default=None)
     p.add_argument("-f", "--fill-value", type=_parse_fill_value, default=None)
@@ -124,6 +129,8 @@ def _add_reencode_args(p: argparse.ArgumentParser) -> None:
     p.add_argument("--attributes", default=None)
     p.add_argument("--attributes-append", default=None)
     p.add_argument("--chunk-limit", dest="filter_chunk_limit", type=int, default=None)
+    p.add_argument("--skip-empty-chunks", dest="filter_skip_empty_chunks", action="store_true",
+                   help=SKIP_EMPTY_HELP)
 
 
 def _reencode_of(a) -> dict:
@@ -154,6 +161,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--tmp", default=None, help="directory for temporary ($name) arrays")
     ap.add_argument("--chunk-limit", type=int, default=None)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--skip-empty-chunks", action="store_true", help=SKIP_EMPTY_HELP)
     ap.add_argument("--stats", action="store_true", help="print per-filter stats as JSON")
     ap.add_argument("--gpus", type=int, default=1,
                     help="split every store step over this many GPUs (one process each) by "
@@ -488,10 +496,13 @@ def read_to_device(path, device: int, nthreads: int = 0, start=None, shape=None)
     return x.view(torch.bfloat16) if info.data_type == "bfloat16" else x
 
 
-def write_from_device(path, x, nthreads: int = 0, start=None) -> None:
+def write_from_device(path, x, nthreads: int = 0, start=None) -> int:
     """A device tensor (the box at `start`, default the whole array at `path`) into the store,
     overlapped chunk row by chunk row: row k+1 is copied device-to-host into one of two pinned
-    buffers while a host thread encodes row k."""
+    buffers while a host thread encodes row k. When the calling thread elides empty chunks
+    (store.set_store_empty_chunks(False)) the row's inner chunks are tested on the device first
+    (filter.chunk_occupancy): a row of nothing but the fill value is not copied, and the encoder
+    gets the map. Returns the number of chunks elided."""
     import torch
     from concurrent.futures import ThreadPoolExecutor
     if x.dtype == torch.bfloat16:
@@ -508,16 +519,42 @@ def write_from_device(path, x, nthreads: int = 0, start=None) -> None:
     nbuf = min(2, len(spans))
     bufs = [torch.empty((rows * plane,), dtype=x.dtype, pin_memory=True) for _ in range(nbuf)]
     futs = [None] * nbuf
+    store_all = S.store_empty_chunks()
+    fill = None
+    if not store_all:  # the fill value's bits, as the tensor's type (bfloat16 travels as uint16)
+        from . import filter as F
+        fill = hex(F.fill_value_bits(S.fill_value_of(path), info.data_type))
+    elided = 0
+
+    def write(h, origin, occ):  # on the encoder thread, with the caller's setting
+        S.set_store_empty_chunks(store_all)
+        S.write_array(path, h, origin, nthreads, occupied=occ)
+        return S.last_elided()[0]
+
+    def skip(origin, row_shape):  # a row of fill: no copy; its files, if any, are removed
+        S.set_store_empty_chunks(store_all)
+        S.write_empty(path, origin, row_shape, nthreads)
+        return S.last_elided()[0]
+
     with ThreadPoolExecutor(1) as ex:
         for k, (a, b) in enumerate(spans):
             if futs[k % nbuf] is not None:
-                futs[k % nbuf].result()  # this buffer's previous row is encoded
+                elided += futs[k % nbuf].result()  # this buffer's previous row is encoded
+                futs[k % nbuf] = None
+            row = x[a - start[0]:b - start[0]]
+            occ = None
+            if not store_all:
+                occ = F.chunk_occupancy(row, info.inner_chunk_shape, fill).cpu().numpy()
+                if not occ.any():
+                    futs[k % nbuf] = ex.submit(skip, [a] + start[1:], [b - a] + shape[1:])
+                    continue
             h = bufs[k % nbuf][:(b - a) * plane].view([b - a] + shape[1:])
-            h.copy_(x[a - start[0]:b - start[0]])
-            futs[k % nbuf] = ex.submit(S.write_array, path, h.numpy(), [a] + start[1:], nthreads)
+            h.copy_(row)
+            futs[k % nbuf] = ex.submit(write, h.numpy(), [a] + start[1:], occ)
         for f in futs:
             if f is not None:
-                f.result()
+                elided += f.result()
+    return elided
 
 
 def plan_pointwise_fusion(names: list, fuse: bool = True, max_ops: int = 8) -> list:
@@ -618,7 +655,7 @@ def run_device_chain(steps: list, paths: list, device: int = 0, nthreads: int = 
             results.append(st)
         x, x_dt, x_chunk = y, out_info.data_type, out_info.chunk_shape
     t2 = time.perf_counter()
-    write_from_device(paths[-1], x, nthreads)
+    results[-1]["chunks_elided"] = write_from_device(paths[-1], x, nthreads)
     S.publish_metadata(paths[-1])  # finished
     results[-1]["encode_s"] = time.perf_counter() - t2
     return results
@@ -630,6 +667,7 @@ def _rows_worker(name: str, src: str, dst: str, params: dict, device: int, rows,
     no metadata writes (the parent writes zarr.json once every row is done). `env`: the memory
     budget of this process (ZT_STORE_HOST_MEMORY / ZT_STORE_DEVICE_MEMORY, its share)."""
     os.environ.update(env or {})
+    S.set_store_empty_chunks(params.get("store_empty_chunks", True))
     cols = None
     if isinstance(rows, tuple) and len(rows) == 2 and isinstance(rows[0], tuple):
         rows, cols = rows  # ((row range), (column range)): a (t, z) block
@@ -690,6 +728,7 @@ def run_rows_parallel(name: str, src: str, dst: str, params: dict, out_shape, gp
     devices = devices or list(range(gpus))
     per = max(1, (nthreads or min(16, os.cpu_count() or 1)) // gpus)
     params = dict(params)
+    params["store_empty_chunks"] = S.store_empty_chunks()  # the processes inherit the setting
     if params.get("chunk_limit"):  # the reference's limit is per process: split it N ways
         params["chunk_limit"] = max(1, int(params["chunk_limit"]) // gpus)
     # each process budgets its share of host memory, and of device memory where processes share
@@ -733,12 +772,17 @@ def _device_ok(device: int) -> bool:
 def run(steps: list, exists: str = "erase", tmp: str | None = None,
         chunk_limit: int | None = None, device: int = 0, stats: bool = False,
         log=print, device_chain: bool = True, gpus: int = 1, gpu_devices=None,
-        fuse_pointwise: bool = True) -> list:
+        fuse_pointwise: bool = True, skip_empty_chunks: bool = False) -> list:
     """Run a list of filter steps (the run-config form); returns the per-step stats. gpus > 1:
     every store step is split over that many processes by output chunk rows (one per GPU;
     `gpu_devices` maps process g to a device, default g); device-resident chains are then off.
     fuse_pointwise=False launches the per-element steps of a device-resident chain one by one
-    (the same results, more passes over HBM)."""
+    (the same results, more passes over HBM). skip_empty_chunks: every output is written without
+    the chunks that hold nothing but the fill value (store.set_store_empty_chunks(False) for the
+    run; the setting of the calling thread is put back afterwards)."""
+    store_all_before = S.store_empty_chunks()
+    if skip_empty_chunks:
+        S.set_store_empty_chunks(False)
     if gpus > 1:
         device_chain = False
     tmp_root = tmp or tempfile.gettempdir()
@@ -876,6 +920,7 @@ def run(steps: list, exists: str = "erase", tmp: str | None = None,
             results.extend(res)
             i = j + 1
     finally:
+        S.set_store_empty_chunks(store_all_before)
         if sys.stderr.isatty():
             S.set_progress_callback(None)
         for d in made:
@@ -904,7 +949,8 @@ def main(argv=None) -> int:
     try:
         run(steps, a.exists, a.tmp, a.chunk_limit, a.device, a.stats,
             device_chain=not a.no_device_chain, gpus=a.gpus,
-            fuse_pointwise=not a.no_pointwise_fusion)
+            fuse_pointwise=not a.no_pointwise_fusion,
+            skip_empty_chunks=a.skip_empty_chunks or getattr(a, "filter_skip_empty_chunks", False))
     except _abi.FilterError as e:
         print(f"Error: {e}", file=sys.stderr)
         return 1

@@ -558,8 +558,10 @@ def run(input_path, output_path, factor=None, max_levels: int = 10, discrete: bo
         gaussian_sigma=None, gaussian_kernel_half_size=None, physical_size=None,
         physical_units=None, group_attributes=None, reencoding=None, log=print,
         device_resident: bool = True, chunk_limit: int = 0, gpus: int = 1,
-        gpu_devices=None) -> dict:
-    """zarrs_ome (zarrs_ome.rs:156-760). gpus > 1: one process per GPU — without a Gaussian the
+        gpu_devices=None, skip_empty_chunks: bool = False) -> dict:
+    """zarrs_ome (zarrs_ome.rs:156-760). skip_empty_chunks: the levels this command computes are
+    written without the chunks that hold nothing but the fill value (zarrs' store_empty_chunks =
+    false; level 0, a copy of the input's files, is left as it is). gpus > 1: one process per GPU — without a Gaussian the
     levels are split by octant ownership (run_octants), with one every level is split by output
     chunk rows (zarrs_filter.run_rows_parallel); `gpu_devices` maps process g to a device."""
     t0 = time.perf_counter()
@@ -591,6 +593,11 @@ def run(input_path, output_path, factor=None, max_levels: int = 10, discrete: bo
                            else group_attributes)
     # octant workers (gpus > 1, no Gaussian) spawned now, so their start-up overlaps this
     # process's preparation; unused (and shut down) if the levels do not take the octant path
+    store_all_before = S.store_empty_chunks()
+    env_before = os.environ.get(S.STORE_EMPTY_CHUNKS_ENV)
+    if skip_empty_chunks:  # this thread, and through the environment the worker processes
+        S.set_store_empty_chunks(False)
+        os.environ[S.STORE_EMPTY_CHUNKS_ENV] = "0"
     pool = octant_pool(gpus, list(gpu_devices or range(gpus))) if gpus > 1 and gauss is None \
         else None
     try:
@@ -598,6 +605,12 @@ def run(input_path, output_path, factor=None, max_levels: int = 10, discrete: bo
                     device, nthreads, gauss, physical_size, physical_units, group_attrs, reencoding,
                     log, device_resident, chunk_limit, gpus, gpu_devices, pool, t0)
     finally:
+        S.set_store_empty_chunks(store_all_before)
+        if skip_empty_chunks:
+            if env_before is None:
+                os.environ.pop(S.STORE_EMPTY_CHUNKS_ENV, None)
+            else:
+                os.environ[S.STORE_EMPTY_CHUNKS_ENV] = env_before
         if pool is not None:
             # every task is done here; the workers' exit (device teardown, ~0.8 s) need not hold
             # up the caller
@@ -812,7 +825,8 @@ def main(argv=None) -> int:
             0, a.gaussian_sigma, a.gaussian_kernel_half_size,
             a.physical_size, a.physical_units, a.group_attributes, enc,
             device_resident=not a.no_device_resident, chunk_limit=a.filter_chunk_limit or 0,
-            gpus=a.gpus, gpu_devices=a.gpu_devices)
+            gpus=a.gpus, gpu_devices=a.gpu_devices,
+            skip_empty_chunks=a.filter_skip_empty_chunks)
     except _abi.FilterError as e:
         print(f"Error: {e}", file=sys.stderr)
         return 1
