@@ -254,6 +254,37 @@ int zt_gradient_magnitude_apply_array(zt_ctx* ctx, int dtype_in, const void* in,
                                       void* out, const int64_t* shape, int ndim,
                                       const int64_t* chunk_shape, int op);
 
+/* ---- Rank filters: minimum, median, maximum (an extension; the reference has none) ---------- */
+
+/* Output k selects one element of the window in[clamp(k_a + i_a, 0, n_a - 1)], i_a in
+ * [-h_a, h_a] on every axis, h = kernel_half_size (replicate edges, N = prod(2 h_a + 1) entries):
+ * the smallest, the entry of rank (N - 1) / 2 of the sorted window, or the largest. Integers order
+ * by value, bool false < true, floats by the key bits ^ (sign ? all ones : sign bit) compared
+ * unsigned (-NaN < -inf < ... < -0.0 < +0.0 < ... < +inf < +NaN). The result is the selected
+ * element's storage bits, unchanged; another output type is its Rust `as` cast. */
+enum { ZT_RANK_MINIMUM = 0, ZT_RANK_MEDIAN = 1, ZT_RANK_MAXIMUM = 2 };
+/* All 13 types in and out. */
+int zt_rank_filter_is_compatible(int dtype_in, int dtype_out);
+/* nin * 3 * size_in + nout * (size_in + size_out) with nin = prod(chunk_a + 2 h_a): the input
+ * block, two pass buffers and the selected block before the cast. */
+int zt_rank_filter_memory_per_chunk(int dtype_in, int dtype_out, const int64_t* chunk_shape,
+                                    int ndim, const int64_t* kernel_half_size, uint64_t* bytes);
+/* The filter of a C-order device block (edges clamp at the block bounds), writing the region
+ * [out_start, out_start + out_shape) to `out` (C order, out_shape). kind: ZT_RANK_*;
+ * kernel_half_size: ndim non-negative entries; a median window of more than 4096 entries is
+ * ZT_ERR_INVALID_PARAMETERS. 3-D blocks with h = (1, 1, 1) and 1/2/4-byte elements run one fused
+ * z-march; otherwise minimum / maximum run one pass per axis and the median bisects per output. */
+int zt_rank_filter_apply_ndarray(zt_ctx* ctx, int dtype_in, const void* in,
+                                 const int64_t* in_shape, int ndim, const int64_t* out_start,
+                                 const int64_t* out_shape, int dtype_out, void* out, int kind,
+                                 const int64_t* kernel_half_size);
+/* The chunk loop over a device-resident C-order array: every chunk with its kernel_half_size
+ * halo, which equals one pass over the whole array. */
+int zt_rank_filter_apply_array(zt_ctx* ctx, int dtype_in, const void* in, int dtype_out,
+                               void* out, const int64_t* shape, int ndim,
+                               const int64_t* chunk_shape, int kind,
+                               const int64_t* kernel_half_size);
+
 /* ---- Summed-area table (src/filter/filters/summed_area_table.rs) ---------------------------- */
 
 /* SummedAreaTable::is_compatible (summed_area_table.rs:110-134): all 13 types in and out. */
@@ -558,6 +589,13 @@ int zt_store_gaussian(const char* in_path, const char* out_path, int dtype_out,
 int zt_store_gradient_magnitude(const char* in_path, const char* out_path, int dtype_out,
                                 const char* encoding_json, int op, int device, int64_t row_begin,
                                 int64_t row_end, int nthreads, int flags, zt_store_stats* stats);
+/* zarrs_filter median | minimum | maximum IN OUT KERNEL_HALF_SIZE [--data-type T] over a store:
+ * as zt_store_guided_filter, halo = kernel_half_size; kind: ZT_RANK_* (another value is
+ * ZT_ERR_INVALID_PARAMETERS). */
+int zt_store_rank_filter(const char* in_path, const char* out_path, int dtype_out,
+                         const char* encoding_json, int kind, const int64_t* kernel_half_size,
+                         int device, int64_t row_begin, int64_t row_end, int nthreads, int flags,
+                         zt_store_stats* stats);
 /* zarrs_filter summed-area-table IN OUT [--data-type T] over a store (SummedAreaTable::apply,
  * summed_area_table.rs:144-253) in one read and one write of the store (the reference: one of
  * each per axis): every chunk row along axis 0 is summed along its other axes on its own, and

@@ -6,6 +6,9 @@ per operation with its HBM roofline fraction and a CPU baseline (the oracle's C 
 one thread, on a bounded sample of the same workload).
 `--only gradient`: the gradient magnitude (Sobel) on 1024^3 f32, alternated with the Gaussian at
 kernel_half_size 1 on the same volume (its yardstick), windows of at least half a second.
+`--only rank`: the rank filters (minimum, median, maximum) at kernel_half_size 1 on 1024^3 f32 and
+u8, alternated with the same Gaussian yardstick; the median once more through the generic
+bisection kernel.
 `--only sat`: the summed-area table on 1024^3 float32 -> float32 and uint16 -> uint64, each
 alternated with the reencode cast of the same type pair on the same volume (one read and one
 write per voxel: the streaming yardstick).
@@ -193,6 +196,97 @@ def bench_gradient(n, rounds=5, window_s=0.5):
             "yardstick": {"op": "gaussian sigma 1,1,1 half 1,1,1 (device-resident), same volume, "
                                 "windows alternated with the gradient's", **y_},
             "ratio_to_yardstick": round(g["ms"] / y_["ms"], 4)}
+
+
+def bench_rank(n, dtype, rounds=5, window_s=0.5):
+    """The rank filters (minimum, median, maximum) at kernel_half_size 1,1,1 on n^3 `dtype`
+    (float32 or uint8) through RankFilter.apply, alternated in one run with the Gaussian at sigma
+    1,1,1 / kernel_half_size 1,1,1 on the same volume (the same 3x3x3 footprint and algorithmic
+    bytes: the yardstick of the gradient magnitude). Windows as bench_gradient. The median is also
+    timed once through the generic bisection kernel (the same volume as a 4-D array).
+    Algorithmic bytes: one read and one write of every voxel."""
+    import math
+    import numpy as np
+    import torch
+    import zarrs_tools_amd as zt
+    from tests import rank_ref
+    ctx = zt.default_context(0)
+    if dtype == "float32":
+        x = zt.synth_step_noise_f32((n, n, n))
+    else:  # the low byte of the u16 noise: 256 values
+        x = (zt.synth_u16((n, n, n)).view(torch.int16) & 0xFF).to(torch.uint8)
+    esz = x.element_size()
+    y = torch.empty_like(x)
+    chunk = (min(n, 256),) * 3
+    a_in, a_out = zt.DeviceArray(x, chunk, dtype), zt.DeviceArray(y, chunk, dtype)
+    gs = zt.Gaussian([1.0] * 3, [1] * 3)
+    stream = torch.cuda.current_stream()
+    filters = {k: zt.RankFilter(k, (1, 1, 1)) for k in ("minimum", "median", "maximum")}
+    ops = {k: (lambda f=f: f.apply(a_in, a_out, ctx=ctx)) for k, f in filters.items()}
+    ops["gaussian"] = lambda: gs.apply(a_in, a_out, ctx=ctx)
+    # parity (bit-exact) of the corner region whose inputs lie in the block copied back
+    m = min(n - 1, 32)
+    blk = x[:m + 1, :m + 1, :m + 1].cpu().numpy()
+    exact = {}
+    for k in filters:
+        ops[k]()
+        torch.cuda.synchronize()
+        ref = rank_ref.apply_ndarray(blk, k, (1, 1, 1), dtype)[:m, :m, :m]
+        exact[k] = bool(np.array_equal(y[:m, :m, :m].cpu().numpy(), ref))
+    reps = {}
+    for k, fn in ops.items():  # warm-up, then calls per window until a window lasts window_s
+        r = 8
+        while True:
+            t = timed(fn, stream, r)
+            if t * r >= window_s * 1e3:
+                break
+            r = math.ceil(window_s * 1e3 / t * 1.05) + 1
+        reps[k] = r
+    ms = {k: [] for k in ops}
+    for _ in range(rounds):
+        for k, fn in ops.items():
+            ms[k].append(timed(fn, stream, reps[k]))
+    # the median once through the generic bisection kernel, and its parity with the fused one:
+    # the same volume as a 4-D array with a unit first axis and half size 0 there has the same
+    # windows, and only rank 3 takes the fused kernel
+    ops["median"]()
+    fused_out = y.clone()
+    g_in = zt.DeviceArray(x.view(1, n, n, n), (1,) + chunk, dtype)
+    g_out = zt.DeviceArray(y.view(1, n, n, n), (1,) + chunk, dtype)
+    med4 = zt.RankFilter("median", (0, 1, 1, 1))
+    generic_ms = timed(lambda: med4.apply(g_in, g_out, ctx=ctx), stream, 1)
+    generic_same = bool(torch.equal(y, fused_out))
+    del fused_out
+
+    def line(k):
+        v = sorted(ms[k])
+        med = v[len(v) // 2]
+        gbs = n ** 3 * 2 * esz / (med / 1e3) / 1e9
+        return {"ms": round(med, 4), "ms_min": round(v[0], 4), "ms_max": round(v[-1], 4),
+                "spread": round((v[-1] - v[0]) / med, 4), "windows_ms": [round(t, 4) for t in ms[k]],
+                "calls_per_window": reps[k],
+                "gib_per_s": round(n ** 3 * esz / 2 ** 30 / (med / 1e3), 3),
+                "roofline": {"bound": "hbm", "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS,
+                             "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4),
+                             "algorithmic_bytes": n ** 3 * 2 * esz}}
+
+    y_ = line("gaussian")
+    out = []
+    for k in filters:
+        r = line(k)
+        res = {"op": f"{k} half 1,1,1 (device-resident, fused z-march)",
+               "config": {"shape": [n] * 3, "dtype": dtype, "chunk": list(chunk),
+                          "rounds": rounds, "window_s": window_s},
+               "parity_bit_exact": exact[k], **r,
+               "yardstick": {"op": "gaussian sigma 1,1,1 half 1,1,1 (device-resident), same "
+                                   "volume, windows alternated with the filter's", **y_},
+               "ratio_to_yardstick": round(r["ms"] / y_["ms"], 4)}
+        if k == "median":
+            res["generic_bisection"] = {"ms": round(generic_ms, 4), "calls": 1,
+                                        "equals_fused": generic_same,
+                                        "ratio_to_fused": round(generic_ms / r["ms"], 3)}
+        out.append(res)
+    return out
 
 
 def bench_sat(n, din, dout, rounds=5, window_s=0.5):
@@ -741,6 +835,10 @@ def main():
         print(json.dumps(bench_gaussian(a.gaussian_size, a.reps)), flush=True)
     if "gradient" in only:  # with its Gaussian half-size-1 yardstick, alternated
         print(json.dumps(bench_gradient(a.gaussian_size)), flush=True)
+    if "rank" in only:  # each with the Gaussian half-size-1 yardstick, alternated
+        for dt in ("float32", "uint8"):
+            for res in bench_rank(a.gaussian_size, dt):
+                print(json.dumps(res), flush=True)
     if "sat" in only:  # each with its reencode-cast yardstick, alternated
         for din, dout in (("float32", "float32"), ("uint16", "uint64")):
             print(json.dumps(bench_sat(a.gaussian_size, din, dout)), flush=True)

@@ -24,8 +24,12 @@ from .filter import (  # noqa: E402
     GradientMagnitude,
     GuidedFilter,
     Histogram,
+    Maximum,
+    Median,
+    Minimum,
     PointwiseProgram,
     Range,
+    RankFilter,
     Reencode,
     ReplaceValue,
     Rescale,
@@ -55,4 +59,5 @@ __all__ = [
     "Histogram", "Range", "combine_histograms", "combine_ranges",
     "Compare", "combine_compares",
     "chunk_occupancy",
+    "RankFilter", "Median", "Minimum", "Maximum",
 ]

@@ -67,6 +67,10 @@ _lib = None
 # ZT_GM_* (GradientMagnitudeOperator, gradient_magnitude.rs:24-29)
 GM_OPERATORS = {"sobel": 0, "central_difference": 1}
 
+# ZT_RANK_* (the rank filters' kinds)
+RANK_KINDS = {"minimum": 0, "median": 1, "maximum": 2}
+RANK_MEDIAN_MAX_WINDOW = 4096
+
 # ZT_PW_* (zt_pointwise_op.kind); crop is a reencode of a sub-box
 PW_REENCODE, PW_RESCALE, PW_CLAMP, PW_EQUAL, PW_REPLACE_VALUE = range(5)
 PW_ADD_FIRST = 1
@@ -187,6 +191,16 @@ def lib() -> ctypes.CDLL:
                                                  vp, c_int], c_int),
         "zt_gradient_magnitude_apply_array": ([vp, c_int, vp, c_int, vp, i64p, c_int, i64p,
                                                c_int], c_int),
+        "zt_rank_filter_is_compatible": ([c_int, c_int], c_int),
+        "zt_rank_filter_memory_per_chunk": ([c_int, c_int, i64p, c_int, i64p,
+                                             ctypes.POINTER(ctypes.c_uint64)], c_int),
+        "zt_rank_filter_apply_ndarray": ([vp, c_int, vp, i64p, c_int, i64p, i64p, c_int, vp,
+                                          c_int, i64p], c_int),
+        "zt_rank_filter_apply_array": ([vp, c_int, vp, c_int, vp, i64p, c_int, i64p, c_int,
+                                        i64p], c_int),
+        "zt_store_rank_filter": ([ctypes.c_char_p, ctypes.c_char_p, c_int, ctypes.c_char_p, c_int,
+                                  i64p, c_int, ctypes.c_int64, ctypes.c_int64, c_int, c_int,
+                                  ctypes.POINTER(StoreStats)], c_int),
         "zt_summed_area_table_is_compatible": ([c_int, c_int], c_int),
         "zt_summed_area_table_memory_per_chunk": ([c_int, c_int, i64p, c_int,
                                                    ctypes.POINTER(ctypes.c_uint64)], c_int),

@@ -1738,6 +1738,69 @@ int zt_store_gradient_magnitude(const char* in_path, const char* out_path, int d
     }
 }
 
+int zt_store_rank_filter(const char* in_path, const char* out_path, int dtype_out,
+                         const char* encoding_json, int kind, const int64_t* kernel_half_size,
+                         int device, int64_t row_begin, int64_t row_end, int nthreads, int flags,
+                         zt_store_stats* stats) {
+    try {
+        if (!in_path || !out_path || !kernel_half_size)
+            return zt::set_last_error(ZT_ERR_INVALID_PARAMETERS, "null argument");
+        if (kind != ZT_RANK_MINIMUM && kind != ZT_RANK_MEDIAN && kind != ZT_RANK_MAXIMUM)
+            return zt::set_last_error(ZT_ERR_INVALID_PARAMETERS, "unknown rank filter kind");
+        Array in = Array::open(in_path);
+        const int nd = in.ndim();
+        int64_t window = 1;
+        for (int d = 0; d < nd; ++d) {
+            if (kernel_half_size[d] < 0)
+                return zt::set_last_error(ZT_ERR_INVALID_PARAMETERS, "negative kernel_half_size");
+            if (kernel_half_size[d] > 2048) window = 4097;
+            else if (window <= 4096) window *= 2 * kernel_half_size[d] + 1;
+        }
+        if (kind == ZT_RANK_MEDIAN && window > 4096)
+            return zt::set_last_error(ZT_ERR_INVALID_PARAMETERS,
+                                      "median window of more than 4096 elements");
+        Array out = build_output(in, out_path, dtype_out, in.shape, encoding_json);
+        const int dt = out.dtype;
+        if (int rc = zt_rank_filter_is_compatible(in.dtype, dt)) return rc;
+        if (flags & ZT_STORE_ERASE_OUTPUT_METADATA) out.erase_metadata();
+        const int64_t halo = kernel_half_size[0], nz = in.shape[0];
+        RowOp op;
+        op.input_planes = [&](int64_t z0, int64_t z1, int64_t& a, int64_t& b) {
+            a = std::max<int64_t>(0, z0 - halo);  // the output rows plus the halo, clamped
+            b = std::min(nz, z1 + halo);
+        };
+        const std::vector<int64_t> shape = in.shape;
+        const std::vector<int64_t> hs(kernel_half_size, kernel_half_size + nd);
+        const int din = in.dtype;
+        int64_t gplane = 1;
+        for (int d = 1; d < nd; ++d) gplane *= shape[d];
+        const uint64_t si = in.esz, so = out.esz;
+        const int64_t out_cz = out.chunk_shape[0];
+        op.scratch_bytes = [&](int64_t planes) -> uint64_t {
+            // zt_rank_filter_memory_per_chunk without the input block (the slab, counted by the
+            // pipeline): two pass buffers and the selected rows before the cast
+            return (uint64_t)planes * gplane * 2 * si +
+                   (uint64_t)std::min(out_cz, nz) * gplane * (si + so);
+        };
+        op.apply = [&](zt_ctx* c, const void* slab, int64_t in0, int64_t in1, void* o, int64_t z0,
+                       int64_t z1) -> int {
+            // the slab is a block that carries the halo or reaches the array edge on axis 0 and
+            // spans the other axes: its result on [z0, z1) is the chunked result
+            std::vector<int64_t> bshape(shape), ostart(nd, 0), oshape(shape);
+            bshape[0] = in1 - in0;
+            ostart[0] = z0 - in0;
+            oshape[0] = z1 - z0;
+            return zt_rank_filter_apply_ndarray(c, din, slab, bshape.data(), nd, ostart.data(),
+                                                oshape.data(), dt, o, kind, hs.data());
+        };
+        run_pipeline(in, out, device, row_begin, row_end, nthreads, op, stats);
+        if (flags & ZT_STORE_FINISH_OUTPUT) out.store_metadata();
+        return ZT_OK;
+    } catch (const std::exception& e) {
+        return report(e);
+    }
+}
+
 int zt_store_summed_area_table(const char* in_path, const char* out_path, int dtype_out,
                                const char* encoding_json, int device, int nthreads, int flags,
                                zt_store_stats* stats) {

@@ -1074,6 +1074,197 @@ int zt_gradient_magnitude_apply_array(zt_ctx* ctx, int dtype_in, const void* in,
                                   op);
 }
 
+// ---- rank filters: minimum, median, maximum (rank.hip; no counterpart in the reference) ----------
+
+namespace {
+
+int rank_args_ok(int kind, const int64_t* half, int ndim) {
+    if (kind != ZT_RANK_MINIMUM && kind != ZT_RANK_MEDIAN && kind != ZT_RANK_MAXIMUM)
+        return fail(ZT_ERR_INVALID_PARAMETERS, "unknown rank filter kind %d", kind);
+    if (!half) return fail(ZT_ERR_INVALID_PARAMETERS, "null kernel_half_size");
+    int64_t window = 1;
+    for (int d = 0; d < ndim; ++d) {
+        if (half[d] < 0) return fail(ZT_ERR_INVALID_PARAMETERS, "negative kernel_half_size");
+        if (half[d] > (int64_t)1 << 30)
+            return fail(ZT_ERR_INVALID_PARAMETERS, "kernel_half_size %lld on axis %d is too large",
+                        (long long)half[d], d);
+        if (kind == ZT_RANK_MEDIAN) {
+            window *= 2 * half[d] + 1;  // <= 4096 * (2^31 + 1) before the check: no overflow
+            if (window > zt::kRankMedianMaxWindow)
+                return fail(ZT_ERR_INVALID_PARAMETERS,
+                            "median window of more than %lld elements",
+                            (long long)zt::kRankMedianMaxWindow);
+        }
+    }
+    return ZT_OK;
+}
+
+size_t rank_align(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+
+// The filter on a C-order block, writing only the output region: the selection in the input
+// type (into `out`, or into scratch when the output type differs), then the `as` cast.
+int run_rank_filter(zt_ctx* ctx, int dtype_in, const void* in, const int64_t* in_shape, int ndim,
+                    const int64_t* out_start, const int64_t* out_shape, int dtype_out, void* out,
+                    int kind, const int64_t* half) {
+    const int64_t nout = numel(out_shape, ndim);
+    if (nout == 0) return ZT_OK;
+    const size_t esz = zt::dtype_size(dtype_in);
+    const int mode = zt::rank_key_mode(dtype_in);
+    const bool cast_out = dtype_out != dtype_in;
+    const size_t sel_bytes = cast_out ? rank_align((size_t)nout * esz) : 0;
+    bool fused = ndim == 3 && half[0] == 1 && half[1] == 1 && half[2] == 1;
+    zt::Rank3 p3{};
+    if (fused) {
+        for (int d = 0; d < 3; ++d) {
+            p3.n[d] = in_shape[d];
+            p3.on[d] = out_shape[d];
+            p3.o0[d] = out_start[d];
+        }
+        fused = zt::rank3_supported(p3, (int)esz);
+    }
+    // minimum / maximum pass by pass: every axis with a window or a cropped extent
+    int axes[ZT_MAX_DIMS], naxes = 0;
+    int64_t maxn = 0;
+    if (!fused && kind != ZT_RANK_MEDIAN) {
+        int64_t cur[ZT_MAX_DIMS];
+        std::copy(in_shape, in_shape + ndim, cur);
+        for (int d = 0; d < ndim; ++d) {
+            if (half[d] == 0 && out_shape[d] == in_shape[d]) continue;
+            cur[d] = out_shape[d];
+            axes[naxes++] = d;
+            maxn = std::max(maxn, numel(cur, ndim));
+        }
+    }
+    const size_t buf_bytes = naxes > 1 ? rank_align((size_t)maxn * esz) : 0;
+    if (sel_bytes + 2 * buf_bytes > 0)
+        if (int rc = ctx->ensure_scratch(sel_bytes + 2 * buf_bytes)) return rc;
+    char* base = static_cast<char*>(ctx->scratch);
+    void* sel = cast_out ? static_cast<void*>(base) : out;  // the selected region, input type
+    void* bufs[2] = {base + sel_bytes, base + sel_bytes + buf_bytes};
+    const void* res = sel;
+    if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev0, ctx->cur));
+    if (fused) {
+        hipError_t e = zt::launch_rank3(in, sel, (int)esz, mode, kind, p3, ctx->cur);
+        if (e != hipSuccess) return hip_fail(e, "rank filter z/y/x march launch");
+    } else if (kind == ZT_RANK_MEDIAN) {
+        zt::RankMedian pm{};
+        pm.ndim = ndim;
+        pm.out_numel = nout;
+        int64_t window = 1;
+        for (int d = 0; d < ndim; ++d) {
+            pm.shape[d] = in_shape[d];
+            pm.half[d] = half[d];
+            pm.out_start[d] = out_start[d];
+            pm.out_shape[d] = out_shape[d];
+            window *= 2 * half[d] + 1;
+        }
+        c_strides(in_shape, ndim, pm.stride);
+        pm.rows = (int)(window / (2 * half[ndim - 1] + 1));
+        pm.rank = (int)((window - 1) / 2);
+        hipError_t e = zt::launch_rank_median(in, sel, (int)esz, mode, pm, ctx->cur);
+        if (e != hipSuccess) return hip_fail(e, "rank filter median launch");
+    } else if (naxes == 0) {
+        res = in;  // the identity on the whole block
+        if (!cast_out) ZT_HIP(hipMemcpyAsync(out, in, (size_t)nout * esz, hipMemcpyDeviceToDevice,
+                                             ctx->cur));
+    } else {
+        int64_t cur[ZT_MAX_DIMS];
+        std::copy(in_shape, in_shape + ndim, cur);
+        const void* src = in;
+        for (int a = 0; a < naxes; ++a) {
+            const int d = axes[a];
+            zt::RankPass p{};
+            p.outer = numel(cur, d);
+            p.n = cur[d];
+            p.on = out_shape[d];
+            p.o0 = out_start[d];
+            p.h = half[d];
+            p.inner = numel(cur + d + 1, ndim - d - 1);
+            void* dst = a == naxes - 1 ? sel : bufs[a & 1];
+            hipError_t e = zt::launch_rank_pass(src, dst, (int)esz, mode, kind == ZT_RANK_MAXIMUM,
+                                                p, ctx->cur);
+            if (e != hipSuccess) return hip_fail(e, "rank filter pass launch");
+            src = dst;
+            cur[d] = out_shape[d];
+        }
+    }
+    if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev1, ctx->cur));
+    if (cast_out) {
+        hipError_t e = zt::launch_reencode_cast(res, dtype_in, out, dtype_out, nout, ctx->cur);
+        if (e != hipSuccess) return hip_fail(e, "rank filter output cast");
+    }
+    return ZT_OK;
+}
+
+}  // namespace
+
+int zt_rank_filter_is_compatible(int dtype_in, int dtype_out) {
+    // the selection is a matter of storage bits: all 13 types in, and out through the `as` cast
+    return dtypes_ok(dtype_in, dtype_out);
+}
+
+int zt_rank_filter_memory_per_chunk(int dtype_in, int dtype_out, const int64_t* chunk_shape,
+                                    int ndim, const int64_t* kernel_half_size, uint64_t* bytes) {
+    if (int rc = dtypes_ok(dtype_in, dtype_out)) return rc;
+    if (int rc = check_shape(chunk_shape, ndim, "chunk_shape")) return rc;
+    if (!bytes || !kernel_half_size) return fail(ZT_ERR_INVALID_PARAMETERS, "null pointer");
+    for (int d = 0; d < ndim; ++d)
+        if (kernel_half_size[d] < 0)
+            return fail(ZT_ERR_INVALID_PARAMETERS, "negative kernel_half_size");
+    // the input block, two pass buffers, and the selected block before the cast
+    uint64_t nin = 1;
+    for (int d = 0; d < ndim; ++d) nin *= (uint64_t)(chunk_shape[d] + 2 * kernel_half_size[d]);
+    const uint64_t nout = (uint64_t)numel(chunk_shape, ndim);
+    const uint64_t si = zt::dtype_size(dtype_in), so = zt::dtype_size(dtype_out);
+    *bytes = nin * 3 * si + nout * (si + so);
+    return ZT_OK;
+}
+
+int zt_rank_filter_apply_ndarray(zt_ctx* ctx, int dtype_in, const void* in,
+                                 const int64_t* in_shape, int ndim, const int64_t* out_start,
+                                 const int64_t* out_shape, int dtype_out, void* out, int kind,
+                                 const int64_t* kernel_half_size) {
+    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = dtypes_ok(dtype_in, dtype_out)) return rc;
+    if (int rc = check_shape(in_shape, ndim, "in_shape")) return rc;
+    if (int rc = rank_args_ok(kind, kernel_half_size, ndim)) return rc;
+    if (!out_start || !out_shape) return fail(ZT_ERR_INVALID_PARAMETERS, "null output region");
+    for (int d = 0; d < ndim; ++d)
+        if (out_start[d] < 0 || out_shape[d] < 0 || out_start[d] + out_shape[d] > in_shape[d])
+            return fail(ZT_ERR_INVALID_PARAMETERS, "output region outside the block on axis %d",
+                        d);
+    if (numel(out_shape, ndim) == 0) return ZT_OK;
+    if (!in || !out) return fail(ZT_ERR_INVALID_PARAMETERS, "null data pointer");
+    if (in == out) return fail(ZT_ERR_INVALID_PARAMETERS, "input and output must differ");
+    DeviceGuard g(ctx->device);
+    return run_rank_filter(ctx, dtype_in, in, in_shape, ndim, out_start, out_shape, dtype_out,
+                           out, kind, kernel_half_size);
+}
+
+int zt_rank_filter_apply_array(zt_ctx* ctx, int dtype_in, const void* in, int dtype_out,
+                               void* out, const int64_t* shape, int ndim,
+                               const int64_t* chunk_shape, int kind,
+                               const int64_t* kernel_half_size) {
+    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = dtypes_ok(dtype_in, dtype_out)) return rc;
+    if (int rc = check_shape(shape, ndim, "shape")) return rc;
+    if (int rc = rank_args_ok(kind, kernel_half_size, ndim)) return rc;
+    if (!chunk_shape) return fail(ZT_ERR_INVALID_PARAMETERS, "null chunk_shape");
+    for (int d = 0; d < ndim; ++d)
+        if (chunk_shape[d] <= 0)
+            return fail(ZT_ERR_INVALID_PARAMETERS, "chunk extent must be positive");
+    if (numel(shape, ndim) == 0) return ZT_OK;
+    if (!in || !out) return fail(ZT_ERR_INVALID_PARAMETERS, "null data pointer");
+    if (in == out) return fail(ZT_ERR_INVALID_PARAMETERS, "input and output must differ");
+    // Every chunk with its kernel_half_size halo (clamped to the array) equals the whole array
+    // with replicate edges at the array bounds: a window index clamps inside a chunk's block only
+    // where it clamps at the array (as for the Gaussian above).
+    int64_t zero[ZT_MAX_DIMS] = {0};
+    DeviceGuard g(ctx->device);
+    return run_rank_filter(ctx, dtype_in, in, shape, ndim, zero, shape, dtype_out, out, kind,
+                           kernel_half_size);
+}
+
 // ---- summed-area table (summed_area_table.rs) ------------------------------------------------
 
 namespace {

@@ -150,6 +150,48 @@ hipError_t launch_gm_accumulate(float* g, const float* sq, int64_t total, bool f
 hipError_t launch_gm_finish(const float* g, int dtype_out, void* out, const NdGeom& geom,
                             hipStream_t s);
 
+// Rank filters (rank.hip): minimum, median, maximum of the replicate-edge window
+// of half sizes h. Elements are handled as their storage bits (esz = 1, 2, 4 or 8 bytes) under an
+// order key chosen by `mode`; kind: kRank* (= ZT_RANK_*).
+enum RankKind : int { kRankMinimum = 0, kRankMedian = 1, kRankMaximum = 2 };
+enum RankKeyMode : int { kRankKeyUnsigned = 0, kRankKeySigned = 1, kRankKeyFloat = 2 };
+constexpr int kRankSegMin = 32;           // fewest output slices per z segment (fused)
+constexpr int64_t kRankMedianMaxWindow = 4096;
+inline int rank_key_mode(int dtype) {
+    switch (dtype) {
+    case 1: case 2: case 3: case 4: return kRankKeySigned;     // kI8 .. kI64
+    case 9: case 10: case 11: case 12: return kRankKeyFloat;   // kBF16, kF16, kF32, kF64
+    default: return kRankKeyUnsigned;                          // kBool, kU8 .. kU64
+    }
+}
+// 3-D, h = (1, 1, 1) in one z-march: C-order input block n[3], the region [o0, o0 + on) written
+// C order (on[3]) in the input type; edges clamp at the block bounds.
+struct Rank3 {
+    int64_t n[3], on[3], o0[3];
+};
+bool rank3_supported(const Rank3& p, int esz);
+int rank3_zseg(const Rank3& p, int64_t* nseg);
+hipError_t launch_rank3(const void* in, void* out, int esz, int mode, int kind, const Rank3& p,
+                        hipStream_t s);
+// Minimum / maximum along one axis: input outer x n x inner (C order), output outer x on x inner,
+// output k covering the input positions [o0 + k - h, o0 + k + h] clamped to the axis.
+struct RankPass {
+    int64_t outer, n, on, o0, h, inner;
+};
+hipError_t launch_rank_pass(const void* in, void* out, int esz, int mode, bool max,
+                            const RankPass& p, hipStream_t s);
+// Median by bisection: the region out_start / out_shape of the C-order block `shape` (C-order
+// `stride`), window half sizes `half`; rows = prod(2 half[d] + 1) over every axis but the last,
+// rank = (N - 1) / 2.
+struct RankMedian {
+    int ndim, rows, rank;
+    int64_t out_numel;
+    int64_t shape[kMaxDims], stride[kMaxDims], half[kMaxDims];
+    int64_t out_start[kMaxDims], out_shape[kMaxDims];
+};
+hipError_t launch_rank_median(const void* in, void* out, int esz, int mode, const RankMedian& p,
+                              hipStream_t s);
+
 // Summed-area table (sat.hip; summed_area_table.rs:47-106): one inclusive running sum along the
 // axis of extent n of a C-order array outer x n x inner, `element += acc` left to right in
 // dtype_out, one thread per lane. in != out: the first pass (inner == 1 only), which casts

@@ -10,6 +10,8 @@ Names, argument meaning and error behaviour follow LDeakin/zarrs_tools 0.7.2:
   - ``GradientMagnitude`` <- src/filter/filters/gradient_magnitude.rs (GradientMagnitude::new(
     operator, chunk_limit), apply_chunk :68, apply_ndarray :109, is_compatible :151,
     memory_per_chunk :177, apply :197)
+  - ``RankFilter`` (``Median``, ``Minimum``, ``Maximum``): an extension with no counterpart in
+    the reference; its semantics are DESIGN.md §3.11
   - ``SummedAreaTable`` <- src/filter/filters/summed_area_table.rs (SummedAreaTable::new(
     chunk_limit), apply_dim :47, is_compatible :110, memory_per_chunk :136, apply :144)
   - ``Reencode``, ``Crop``, ``Rescale``, ``Clamp``, ``Equal``, ``ReplaceValue`` <-
@@ -450,6 +452,139 @@ class GradientMagnitude:
             ctx.handle, DTYPES[input.dtype], _ptr(input.data.contiguous()), DTYPES[output.dtype],
             _ptr(output.data), i64_array(input.shape), nd, i64_array(output.chunk_shape),
             self._op))
+
+
+def rank_kind(kind) -> int:
+    """A rank filter's kind ("minimum", "median", "maximum") as the ABI's ZT_RANK_* code."""
+    code = _abi.RANK_KINDS.get(str(kind).lower())
+    if code is None:
+        raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS,
+                                     f"unknown rank filter {kind!r} (minimum, median or maximum)")
+    return code
+
+
+def check_rank_half(kind: str, half, ndim: Optional[int] = None) -> None:
+    """The limits of a rank filter's kernel_half_size: one non-negative entry per axis, and a
+    median window of at most 4096 entries."""
+    if ndim is not None and len(half) != ndim:
+        raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS,
+                                     f"{kind} kernel_half_size needs one entry per axis")
+    if any(h < 0 for h in half):
+        raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS,
+                                     f"{kind}: negative kernel_half_size")
+    if kind == "median" and math.prod(2 * h + 1 for h in half) > _abi.RANK_MEDIAN_MAX_WINDOW:
+        raise _abi.InvalidParameters(
+            _abi.ERR_INVALID_PARAMETERS,
+            f"median window of more than {_abi.RANK_MEDIAN_MAX_WINDOW} elements")
+
+
+class RankFilter:
+    """`RankFilter(kind, kernel_half_size, chunk_limit)`: the minimum, median or maximum of the
+    window of half sizes kernel_half_size around every element, replicate edges (an extension:
+    the reference has no such filter). The result is one of the window's
+    elements, bit for bit, under a total order (floats: -NaN < -inf < ... < -0.0 < +0.0 < ... <
+    +inf < +NaN); another output type is its `as` cast."""
+
+    def __init__(self, kind: str, kernel_half_size: Sequence[int],
+                 chunk_limit: Optional[int] = None):
+        self._kind = rank_kind(kind)
+        self.kind = str(kind).lower()
+        self._half = tuple(int(h) for h in kernel_half_size)
+        check_rank_half(self.kind, self._half)
+        self.chunk_limit = chunk_limit
+
+    def name(self) -> str:
+        return self.kind
+
+    def kernel_half_size(self) -> tuple:
+        return self._half
+
+    def _args(self, nd: int):
+        check_rank_half(self.kind, self._half, nd)
+        return i64_array(self._half)
+
+    def is_compatible(self, dtype_in: str, dtype_out: str) -> None:
+        for d in (dtype_in, dtype_out):
+            if d not in DTYPES:
+                raise _abi.UnsupportedDataType(_abi.ERR_UNSUPPORTED_DATA_TYPE,
+                                               f"Unsupported data type {d}")
+        check(lib().zt_rank_filter_is_compatible(DTYPES[dtype_in], DTYPES[dtype_out]))
+
+    def memory_per_chunk(self, dtype_in: str, dtype_out: str, chunk_shape) -> int:
+        out = ctypes.c_uint64()
+        half = self._args(len(chunk_shape))
+        check(lib().zt_rank_filter_memory_per_chunk(DTYPES[dtype_in], DTYPES[dtype_out],
+                                                    i64_array(chunk_shape), len(chunk_shape),
+                                                    half, ctypes.byref(out)))
+        return int(out.value)
+
+    def apply_ndarray(self, v, out_subset: Optional[ArraySubset] = None,
+                      dtype_out: Optional[str] = None, ctx: Optional[Context] = None):
+        """The filter of a device block, edges clamped at the block's bounds; returns
+        `out_subset` of the result (whole block by default) as dtype_out (default: the
+        input's)."""
+        torch = _torch()
+        v = v.contiguous()
+        ctx = ctx or default_context(v.device.index)
+        dtype_in = dtype_of(v)
+        dtype_out = dtype_out or dtype_in
+        nd = v.dim()
+        if out_subset is None:
+            out_subset = ArraySubset((0,) * nd, tuple(v.shape))
+        half = self._args(nd)
+        out = torch.empty(out_subset.shape, dtype=torch_dtype(dtype_out), device=v.device)
+        check(lib().zt_rank_filter_apply_ndarray(
+            ctx.handle, DTYPES[dtype_in], _ptr(v), i64_array(v.shape), nd,
+            i64_array(out_subset.start), i64_array(out_subset.shape), DTYPES[dtype_out],
+            _ptr(out), self._kind, half))
+        return out
+
+    def apply_chunk(self, input: DeviceArray, output: DeviceArray, chunk_indices,
+                    ctx: Optional[Context] = None) -> None:
+        """One output chunk from the input chunk plus a halo of kernel_half_size clamped to the
+        array (ArraySubsetOverlap), on device-resident arrays."""
+        subset_output = output.chunk_subset_bounded(chunk_indices)
+        overlap = ArraySubsetOverlap(input.shape, subset_output, self._half)
+        si = overlap.subset_input()
+        block = input.data[tuple(slice(s, s + n) for s, n in zip(si.start, si.shape))]
+        res = self.apply_ndarray(block, overlap.subset_dst_in_src(), output.dtype, ctx)
+        output.data[tuple(slice(s, s + n) for s, n in
+                          zip(subset_output.start, subset_output.shape))] = res
+
+    def apply(self, input: DeviceArray, output: DeviceArray,
+              ctx: Optional[Context] = None) -> None:
+        """Every output chunk (one pass over the array)."""
+        if tuple(output.shape) != tuple(input.shape):
+            raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS,
+                                         "input and output shapes differ")
+        ctx = ctx or default_context(input.data.device.index)
+        nd = len(input.shape)
+        half = self._args(nd)
+        check(lib().zt_rank_filter_apply_array(
+            ctx.handle, DTYPES[input.dtype], _ptr(input.data.contiguous()), DTYPES[output.dtype],
+            _ptr(output.data), i64_array(input.shape), nd, i64_array(output.chunk_shape),
+            self._kind, half))
+
+
+class Median(RankFilter):
+    """`Median(kernel_half_size)`: the entry of rank (N - 1) / 2 of the sorted window."""
+
+    def __init__(self, kernel_half_size: Sequence[int], chunk_limit: Optional[int] = None):
+        super().__init__("median", kernel_half_size, chunk_limit)
+
+
+class Minimum(RankFilter):
+    """`Minimum(kernel_half_size)`: grey-scale erosion by the box of half sizes h."""
+
+    def __init__(self, kernel_half_size: Sequence[int], chunk_limit: Optional[int] = None):
+        super().__init__("minimum", kernel_half_size, chunk_limit)
+
+
+class Maximum(RankFilter):
+    """`Maximum(kernel_half_size)`: grey-scale dilation by the box of half sizes h."""
+
+    def __init__(self, kernel_half_size: Sequence[int], chunk_limit: Optional[int] = None):
+        super().__init__("maximum", kernel_half_size, chunk_limit)
 
 
 class SummedAreaTable:

@@ -412,6 +412,25 @@ def gradient_magnitude(input_path, output_path, operator: str = "sobel",
     return _stats(st)
 
 
+def rank_filter(input_path, output_path, kind: str, kernel_half_size,
+                data_type: Optional[str] = None, device: int = 0, rows=None, nthreads: int = 0,
+                erase: bool = True, finish: bool = True, encoding=None,
+                chunk_limit: int = 0) -> dict:
+    """zarrs_filter median | minimum | maximum INPUT OUTPUT KERNEL_HALF_SIZE [--data-type T];
+    `kind`: "minimum", "median" or "maximum"."""
+    from .filter import rank_kind
+    code = rank_kind(kind)
+    set_chunk_limit(chunk_limit)
+    st = _abi.StoreStats()
+    r0, r1 = (0, -1) if rows is None else (int(rows[0]), int(rows[1]))
+    check(lib().zt_store_rank_filter(_b(input_path), _b(output_path), _dt(data_type),
+                                     _enc(encoding), code,
+                                     i64_array([int(x) for x in kernel_half_size]), int(device),
+                                     r0, r1, int(nthreads), _flags(erase, finish),
+                                     ctypes.byref(st)))
+    return _stats(st)
+
+
 def summed_area_table(input_path, output_path, data_type: Optional[str] = None, device: int = 0,
                       nthreads: int = 0, erase: bool = True, finish: bool = True, encoding=None,
                       chunk_limit: int = 0) -> dict:

@@ -1,6 +1,6 @@
 """``zarrs_filter`` for the on-path filters (guided_filter, downsample, gaussian,
-summed_area_table and the per-element reencode, crop, rescale, clamp, equal, replace_value) over
-Zarr V3 stores.
+summed_area_table, the rank filters median, minimum, maximum and the per-element reencode, crop,
+rescale, clamp, equal, replace_value) over Zarr V3 stores.
 
 Mirrors src/bin/zarrs_filter.rs (LDeakin/zarrs_tools 0.7.2) for the filters this framework
 accelerates:
@@ -10,6 +10,9 @@ accelerates:
                                         | downsample IN OUT STRIDE [--discrete] [--data-type T]
                                         | gaussian IN OUT SIGMA KERNEL_HALF_SIZE [--data-type T]
                                         | summed-area-table IN OUT [--data-type T]
+                                        | median IN OUT KERNEL_HALF_SIZE [--data-type T]
+                                        | minimum IN OUT KERNEL_HALF_SIZE [--data-type T]
+                                        | maximum IN OUT KERNEL_HALF_SIZE [--data-type T]
                                         | reencode IN OUT | crop IN OUT OFFSET SHAPE
                                         | rescale IN OUT MULTIPLY ADD [--add-first]
                                         | clamp IN OUT MIN MAX | equal IN OUT VALUE
@@ -19,14 +22,16 @@ accelerates:
   DownsampleArguments (downsample.rs:20-33, STRIDE comma delimited) and GaussianArguments
   (gaussian.rs:22-30, SIGMA and KERNEL_HALF_SIZE comma delimited, one entry per axis);
   summed-area-table takes none of its own (SummedAreaTableArguments, summed_area_table.rs:22-23);
-  the per-element filters as ReencodeArguments (reencode.rs:20), CropArguments (crop.rs:20-27,
+  median, minimum and maximum (extensions: the reference has no rank filter)
+  take KERNEL_HALF_SIZE, comma delimited, one non-negative entry per axis, the median's window
+  holding at most 4096 elements; the per-element filters as ReencodeArguments (reencode.rs:20), CropArguments (crop.rs:20-27,
   OFFSET and SHAPE comma delimited), RescaleArguments (rescale.rs:20-31), ClampArguments
   (clamp.rs:20-25), EqualArguments (equal.rs:23-34) and ReplaceValueArguments
   (replace_value.rs:23-44); VALUE and REPLACE follow parse_fill_value (a JSON number, true /
   false, NaN, Infinity, -Infinity) and negative numbers parse as values;
 * a JSON run config is a list of {"filter": "guided_filter" | "downsample" | "gaussian" |
-  "summed_area_table" | "reencode" | "crop" | "rescale" | "clamp" | "equal" | "replace_value",
-  "input", "output", ...args (offset, shape, multiply, add, add_first, min, max, value, replace
+  "summed_area_table" | "median" | "minimum" | "maximum" | "reencode" | "crop" | "rescale" |
+  "clamp" | "equal" | "replace_value", "input", "output", ...args (kernel_half_size; offset, shape, multiply, add, add_first, min, max, value, replace
   for the per-element filters), "data_type"}, with "$name" meaning a named temporary array
   under --tmp and an omitted input meaning the previous filter's output (zarrs_filter.rs:106-138,
   :338-381);
@@ -76,7 +81,8 @@ from . import _abi
 from . import store as S
 
 POINTWISE = ("reencode", "crop", "rescale", "clamp", "equal", "replace_value")
-ON_PATH = ("guided_filter", "downsample", "gaussian", "summed_area_table") + POINTWISE
+RANK = ("median", "minimum", "maximum")
+ON_PATH = ("guided_filter", "downsample", "gaussian", "summed_area_table") + RANK + POINTWISE
 
 
 def rows_splittable(name: str) -> bool:
@@ -209,6 +215,18 @@ def build_parser() -> argparse.ArgumentParser:
         p.add_argument("output")
         return p
 
+    # the rank filters (an extension); a negative KERNEL_HALF_SIZE parses as a value and is
+    # rejected as InvalidParameters when the step runs
+    rank_number = re.compile(r"^-\d+(,-?\d+)*$")
+    for name, what in (("median", "median"), ("minimum", "minimum (grey-scale erosion)"),
+                       ("maximum", "maximum (grey-scale dilation)")):
+        rk = sub.add_parser(name, help=f"Apply a {what} filter over a box neighbourhood.")
+        rk._negative_number_matcher = rank_number
+        rk.add_argument("input")
+        rk.add_argument("output")
+        rk.add_argument("kernel_half_size", type=_parse_stride)
+        _add_reencode_args(rk)
+
     re_ = pointwise("reencode", "Reencode an array.")
     _add_reencode_args(re_)
     cr = pointwise("crop", "Crop an array given an offset and shape.")
@@ -252,6 +270,10 @@ def _steps_from_cli(a) -> list:
         return [{"filter": "summed_area_table", "input": a.input, "output": a.output,
                  "data_type": a.data_type, "chunk_limit": a.filter_chunk_limit,
                  **_reencode_of(a)}]
+    if a.filter in RANK:
+        return [{"filter": a.filter, "input": a.input, "output": a.output,
+                 "kernel_half_size": a.kernel_half_size, "data_type": a.data_type,
+                 "chunk_limit": a.filter_chunk_limit, **_reencode_of(a)}]
     own = {"reencode": (), "crop": ("offset", "shape"),
            "rescale": ("multiply", "add", "add_first"), "clamp": ("min", "max"),
            "equal": ("value",), "replace-value": ("value", "replace")}
@@ -370,6 +392,15 @@ def _step_params(step, info):
         return F.Gaussian(sigma, half), tuple(info.shape), dt
     if name == "summed_area_table":
         return F.SummedAreaTable(), tuple(info.shape), dt
+    if name in RANK:
+        half = step.get("kernel_half_size")
+        half = _parse_stride(half) if isinstance(half, str) else half
+        if half is None:
+            raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS,
+                                         f"{name} needs kernel_half_size")
+        half = [int(h) for h in half]
+        F.check_rank_half(name, half, info.ndim)
+        return F.RankFilter(name, half), tuple(info.shape), dt
     stride = step.get("stride")
     stride = _parse_stride(stride) if isinstance(stride, str) else stride
     if not stride or len(stride) != info.ndim:
@@ -678,6 +709,8 @@ def _rows_worker(name: str, src: str, dst: str, params: dict, device: int, rows,
         return S.guided_filter(src, dst, params["epsilon"], params["radius"], cols=cols, **kw)
     if name == "gaussian":
         return S.gaussian(src, dst, params["sigma"], params["kernel_half_size"], **kw)
+    if name in RANK:
+        return S.rank_filter(src, dst, name, params["kernel_half_size"], **kw)
     if name in POINTWISE:
         return _store_pointwise(name, src, dst, params["args"], **kw)
     if name == "downsample_gaussian":  # a zarrs_ome level with --gaussian-sigma
@@ -834,6 +867,10 @@ def run(steps: list, exists: str = "erase", tmp: str | None = None,
         elif name == "summed_area_table":
             params = {}
             log(f"{i}: summed_area_table {src} ({info.data_type} {list(info.shape)}) -> {dst}")
+        elif name in RANK:
+            params = {"kernel_half_size": list(f.kernel_half_size())}
+            log(f"{i}: {name} kernel_half_size={params['kernel_half_size']} "
+                f"{src} ({info.data_type} {list(info.shape)}) -> {dst}")
         elif name in POINTWISE:
             own = ("offset", "shape", "multiply", "add", "add_first", "min", "max", "value",
                    "replace")
@@ -866,6 +903,10 @@ def run(steps: list, exists: str = "erase", tmp: str | None = None,
         elif name == "summed_area_table":
             st = S.summed_area_table(src, dst, data_type=params["data_type"], device=device,
                                      encoding=enc, chunk_limit=limit)
+        elif name in RANK:
+            st = S.rank_filter(src, dst, name, params["kernel_half_size"],
+                               data_type=params["data_type"], device=device, encoding=enc,
+                               chunk_limit=limit)
         elif name in POINTWISE:
             st = _store_pointwise(name, src, dst, params["args"], data_type=params["data_type"],
                                   device=device, encoding=enc, chunk_limit=limit)
