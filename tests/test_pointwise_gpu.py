@@ -17,7 +17,7 @@ import pytest
 from oracle import oracle as O
 from tests import pw_ref as R
 from tests import sat_ref
-from tests.gpu_util import FLOAT_TOL, from_dev, rel_err, to_dev
+from tests.gpu_util import FLOAT_TOL, from_dev, poisoned, rel_err, to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -36,16 +36,7 @@ def V(din, dout):
     return 16 // min(SIZE[din], SIZE[dout])
 
 
-def prefill(shape, dout):
-    """An output buffer that no result equals by accident (as the summed-area-table tests')."""
-    st = O.NP_STORAGE[dout]
-    if dout in ("float16", "bfloat16"):
-        fill = np.full(shape, 0x7FFF, dtype=np.uint16)
-    elif dout in R.FLOATS:
-        fill = np.full(shape, np.nan, dtype=st)
-    else:
-        fill = np.full(shape, np.iinfo(st).max, dtype=st)
-    return to_dev(fill, dout)
+prefill = poisoned  # an output buffer that no result equals by accident (tests/gpu_util.py)
 
 
 def gpu(v, din, filters, douts):
