@@ -368,6 +368,26 @@ int zt_pointwise_apply_ndarray(zt_ctx* ctx, int dtype_in, const void* in, const 
                                int ndim, const int64_t* sub_start, const int64_t* sub_shape,
                                const zt_pointwise_op* ops, int n_ops, void* out);
 
+/* ---- two-array arithmetic (an extension: the reference has no such filter) ------------------- */
+
+/* out[i] = (first[i] as f64  op  second[i] as f64) as TOut. `as` is Rust's (64-bit integers round
+ * to nearest even, half types convert exactly, bool is 0 / 1); op is one IEEE f64 operation, no
+ * contraction, denormals kept; the final cast is rescale's (float -> integer saturates, NaN -> 0,
+ * f64 -> half in one rounding, bool written as uint8). minimum is `y < x ? y : x` and maximum
+ * `y > x ? y : x`: a NaN on either side, or +-0 against -+0, returns x. */
+enum { ZT_AR_ADD = 0, ZT_AR_SUBTRACT = 1, ZT_AR_MULTIPLY = 2, ZT_AR_DIVIDE = 3,
+       ZT_AR_MINIMUM = 4, ZT_AR_MAXIMUM = 5, ZT_AR_ABSOLUTE_DIFFERENCE = 6 };
+/* All 13 types for each of the three arrays, independently; an unknown op is
+ * ZT_ERR_INVALID_PARAMETERS. */
+int zt_arithmetic_is_compatible(int op, int dtype_a, int dtype_b, int dtype_out);
+/* memory_per_chunk: chunk elements x the sum of the three element sizes. */
+int zt_arithmetic_memory_per_chunk(int op, int dtype_a, int dtype_b, int dtype_out,
+                                   const int64_t* chunk_shape, int ndim, uint64_t* bytes);
+/* n contiguous device elements of each array, on the context's stream. The pointers need element
+ * alignment only, each on its own; `out` must not overlap `a` or `b`. n == 0 is a no-op. */
+int zt_arithmetic_apply(zt_ctx* ctx, int op, int dtype_a, const void* a, int dtype_b,
+                        const void* b, int64_t n, int dtype_out, void* out);
+
 /* ---- zarrs_info reductions (src/info/range.rs, src/info/histogram.rs) ------------------------ */
 
 /* The 12 numeric types; ZT_BOOL is ZT_ERR_UNSUPPORTED_DATA_TYPE (the reference reaches
@@ -621,6 +641,20 @@ int zt_store_pointwise(const char* in_path, const char* out_path, int dtype_out,
                        const int64_t* crop_offset, const int64_t* crop_shape, int device,
                        int64_t row_begin, int64_t row_end, int nthreads, int flags,
                        zt_store_stats* stats);
+/* zarrs_filter arithmetic over two stores: out = first op second (zt_arithmetic_apply) on every
+ * chunk row of the first array, no halo. The shapes must be equal (ZT_ERR_INVALID_PARAMETERS,
+ * `Array shapes do not match: [..] vs [..]`, before any device work); the second array may have
+ * another data type, chunk grid, sharding and codecs: for every row the chunks of the second
+ * array that meet the row's planes are decoded into a row of the same shape, so a chunk of the
+ * second array taller than a row is decoded once per row it meets (as zt_store_compare). The
+ * output array is built from the first array (dtype_out < 0: the first array's type;
+ * encoding_json as zt_store_guided_filter). Missing chunks of either array read as that array's
+ * fill value and go through the operator. Rows as zt_store_guided_filter; the host and device
+ * budgets and the chunk limit count both inputs; progress counts output chunks. */
+int zt_store_arithmetic(const char* first_path, const char* second_path, const char* out_path,
+                        int dtype_out, const char* encoding_json, int op, int device,
+                        int64_t row_begin, int64_t row_end, int nthreads, int flags,
+                        zt_store_stats* stats);
 /* One zarrs_ome level with --gaussian-sigma (apply_chunk_continuous_gaussian, zarrs_ome.rs:
  * 236-271): the Gaussian of each downsample input subset (plus its kernel_half_size halo), then
  * the mean downsample of that f32 block to the level's data type. */

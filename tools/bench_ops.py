@@ -22,6 +22,9 @@ noise and on a volume that is 90 % one value.
 `--only compare`: zarrs_validate's comparison (compare.hip) on two 1024^3 float32 arrays, equal,
 1 % differing and all differing, alternated with the range over one float32 run of the same
 bytes.
+`--only arithmetic`: the two-array arithmetic filter (arithmetic.hip) on 1024^3: float32 - float32
+-> float32, uint16 + uint16 -> uint16 and float32 * uint8 -> float32, alternated with Rescale on
+float32 -> float32 (the per-byte yardstick).
 
 Algorithmic bytes: pyramid = level 0 read once + every level written once (2 B per u16
 element; the fused launches never read an intermediate level back); Gaussian = 4 B read + 4 B written per voxel (the separable passes' intermediates are
@@ -704,6 +707,99 @@ def bench_compare(n, rounds=5, window_s=0.4):
     return res
 
 
+def bench_arithmetic(n, rounds=5, window_s=0.5):
+    """The two-array arithmetic filter on n^3 device arrays (arithmetic.hip): float32 - float32 ->
+    float32 (12 B per voxel), uint16 + uint16 -> uint16 (6 B) and float32 * uint8 -> float32
+    (9 B), alternated in one run with Rescale on n^3 float32 -> float32 (8 B per voxel, the
+    streaming yardstick). Windows of at least window_s after a warm-up, `rounds` of each, medians.
+    Bytes: every element of the three streams once. The f32 result is checked against torch."""
+    import math
+    import torch
+    import zarrs_tools_amd as zt
+    ctx = zt.default_context(0)
+    stream = torch.cuda.current_stream()
+    shape, total = (n, n, n), n ** 3
+    a = zt.synth_step_noise_f32(shape)
+    b = a.flip(0).contiguous()
+    out = torch.empty_like(a)
+    ua, ub = zt.synth_u16(shape), zt.synth_u16(shape, seed=7)
+    m8 = ub.view(torch.uint8)[..., ::2].contiguous()  # the low byte of every element
+    # Arrays allocated one after the other lie a power of two apart at n = 1024 (2^32 bytes for
+    # float32), where a lane's accesses to the streams fall on the same place in the address
+    # interleave (profiles/compare.txt). The `_apart` ops use operands carved out of one pool at
+    # distances that are no power of two: 2 MiB more between each pair.
+    pad, at = 2 << 20, 0
+    pool = torch.empty(14 * total + 8 * pad, dtype=torch.uint8, device="cuda")
+
+    def carve(dtype, esz):
+        nonlocal at
+        at += pad
+        t = pool[at:at + total * esz].view(dtype).reshape(shape)
+        at += total * esz
+        return t
+
+    b_ap, out_ap = carve(torch.float32, 4), carve(torch.float32, 4)
+    ub_ap, uout_ap, m8_ap = carve(torch.uint16, 2), carve(torch.uint16, 2), carve(torch.uint8, 1)
+    b_ap.copy_(b)
+    ub_ap.copy_(ub)
+    m8_ap.copy_(m8)
+    uout = torch.empty_like(ua)
+    resc = zt.PointwiseProgram([zt.Rescale(0.5, 1.0)], "float32", ["float32"], shape)
+    sub, add, mul = zt.Arithmetic("subtract"), zt.Arithmetic("add"), zt.Arithmetic("multiply")
+    exact = True
+    for o, bb in ((out, b), (out_ap, b_ap)):
+        sub.apply_ndarray(a, bb, out=o, ctx=ctx)
+        exact = exact and bool(torch.equal(o, a - b))
+    mul.apply_ndarray(a, m8_ap, out=out_ap, ctx=ctx)
+    exact = exact and bool(torch.equal(out_ap, a * m8.to(torch.float32)))
+    ops = {"rescale_f32": (lambda: resc.run(a, out, ctx), 8, (a, out)),
+           "rescale_f32_apart": (lambda: resc.run(a, out_ap, ctx), 8, (a, out_ap)),
+           "subtract_f32_f32_f32": (lambda: sub.apply_ndarray(a, b, out=out, ctx=ctx), 12,
+                                    (a, b, out)),
+           "subtract_f32_f32_f32_apart": (lambda: sub.apply_ndarray(a, b_ap, out=out_ap, ctx=ctx),
+                                          12, (a, b_ap, out_ap)),
+           "add_u16_u16_u16": (lambda: add.apply_ndarray(ua, ub, out=uout, ctx=ctx), 6,
+                               (ua, ub, uout)),
+           "add_u16_u16_u16_apart": (lambda: add.apply_ndarray(ua, ub_ap, out=uout_ap, ctx=ctx),
+                                     6, (ua, ub_ap, uout_ap)),
+           "multiply_f32_u8_f32_apart": (lambda: mul.apply_ndarray(a, m8_ap, out=out_ap, ctx=ctx),
+                                         9, (a, m8_ap, out_ap))}
+    reps = {}
+    for k, (fn, _, _) in ops.items():  # warm-up, then calls per window until it lasts window_s
+        r = 1
+        while True:
+            t = timed(fn, stream, r)
+            if t * r >= window_s * 1e3:
+                break
+            r = math.ceil(window_s * 1e3 / t * 1.05) + 1
+        reps[k] = r
+    ms = {k: [] for k in ops}
+    for _ in range(rounds):
+        for k, (fn, _, _) in ops.items():
+            ms[k].append(timed(fn, stream, reps[k]))
+    res = {"op": "arithmetic on two arrays (device-resident)",
+           "config": {"shape": [n] * 3, "rounds": rounds, "window_s": window_s},
+           "exact": exact, "ops": {}}
+    for k, (_, per, arrays) in ops.items():
+        v = sorted(ms[k])
+        med = v[len(v) // 2]
+        nbytes = total * per
+        gbs = nbytes / (med / 1e3) / 1e9
+        res["ops"][k] = {"ms": round(med, 4), "ms_min": round(v[0], 4), "ms_max": round(v[-1], 4),
+                         "spread": round((v[-1] - v[0]) / med, 4), "calls_per_window": reps[k],
+                         "bytes_per_voxel": per, "GB/s": round(gbs, 1),
+                         "GiB/s": round(nbytes / (med / 1e3) / 2 ** 30, 1),
+                         "hbm_frac": round(gbs / HBM_PEAK_GBS, 4),
+                         "ns_per_KiB": round(med * 1e6 / (nbytes / 1024), 5),
+                         "address_distance": [t.data_ptr() - arrays[0].data_ptr()
+                                              for t in arrays[1:]]}
+    for k in ops:  # each against the yardstick placed the same way
+        y = res["ops"]["rescale_f32_apart" if k.endswith("_apart") else "rescale_f32"]
+        res["ops"][k]["per_byte_ratio_to_rescale"] = round(
+            res["ops"][k]["ns_per_KiB"] / y["ns_per_KiB"], 4)
+    return res
+
+
 def bench_guided4d(shape, chunk, radius, reps):
     """Config T per GPU: a (T, Z, Y, X) f32 time-series share, chunks
     (4, 256, 256, 256), eps 2500. 4-D arrays take the separable per-axis path."""
@@ -850,6 +946,8 @@ def main():
             print(json.dumps(res), flush=True)
     if "compare" in only:  # with the range over the same bytes, alternated
         print(json.dumps(bench_compare(a.gaussian_size)), flush=True)
+    if "arithmetic" in only:  # with the float32 rescale yardstick, alternated
+        print(json.dumps(bench_arithmetic(a.gaussian_size)), flush=True)
 
 
 if __name__ == "__main__":

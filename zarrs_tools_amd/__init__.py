@@ -10,6 +10,8 @@ from ._abi import DTYPES, FilterError, InvalidParameters, UnsupportedDataType, l
 lib()  # fail at import time if the native library is absent
 
 from .filter import (  # noqa: E402
+    ARITHMETIC_OPERATORS,
+    Arithmetic,
     ArraySubset,
     ArraySubsetOverlap,
     Clamp,
@@ -60,4 +62,5 @@ __all__ = [
     "Compare", "combine_compares",
     "chunk_occupancy",
     "RankFilter", "Median", "Minimum", "Maximum",
+    "Arithmetic", "ARITHMETIC_OPERATORS",
 ]

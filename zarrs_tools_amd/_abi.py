@@ -76,6 +76,10 @@ PW_REENCODE, PW_RESCALE, PW_CLAMP, PW_EQUAL, PW_REPLACE_VALUE = range(5)
 PW_ADD_FIRST = 1
 PW_MAX_OPS = 8
 
+# ZT_AR_* (the two-array arithmetic filter's operators)
+AR_OPERATORS = {"add": 0, "subtract": 1, "multiply": 2, "divide": 3, "minimum": 4, "maximum": 5,
+                "absolute_difference": 6}
+
 
 class PointwiseOp(ctypes.Structure):
     """zt_pointwise_op (include/zarrs_tools_amd.h)."""
@@ -217,6 +221,14 @@ def lib() -> ctypes.CDLL:
                                 ctypes.POINTER(PointwiseOp), c_int, i64p, i64p, c_int,
                                 ctypes.c_int64, ctypes.c_int64, c_int, c_int,
                                 ctypes.POINTER(StoreStats)], c_int),
+        "zt_arithmetic_is_compatible": ([c_int, c_int, c_int, c_int], c_int),
+        "zt_arithmetic_memory_per_chunk": ([c_int, c_int, c_int, c_int, i64p, c_int,
+                                            ctypes.POINTER(ctypes.c_uint64)], c_int),
+        "zt_arithmetic_apply": ([vp, c_int, c_int, vp, c_int, vp, ctypes.c_int64, c_int, vp],
+                                c_int),
+        "zt_store_arithmetic": ([ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, c_int,
+                                 ctypes.c_char_p, c_int, c_int, ctypes.c_int64, ctypes.c_int64,
+                                 c_int, c_int, ctypes.POINTER(StoreStats)], c_int),
         "zt_range_is_compatible": ([c_int], c_int),
         "zt_histogram_is_compatible": ([c_int], c_int),
         "zt_range_init": ([vp, vp], c_int),

@@ -146,6 +146,13 @@ std::vector<int64_t> c_strides(const std::vector<int64_t>& shape) {
     return st;
 }
 
+// `{:?}` of a Vec<u64>
+std::string shape_list(const std::vector<int64_t>& v) {
+    std::string s = "[";
+    for (size_t i = 0; i < v.size(); ++i) s += (i ? ", " : "") + std::to_string(v[i]);
+    return s + "]";
+}
+
 // every chunk index of the chunk rows [r0, r1) along axis 0
 // Chunks of rows [r0, r1) along axis 0 whose axis-1 index lies in [c0, c1) (c1 < 0: all).
 std::vector<std::vector<int64_t>> chunks_in_rows(const Array& a, int64_t r0, int64_t r1,
@@ -613,11 +620,22 @@ struct RowOp {
     std::function<int(zt_ctx*, const void* slab, int64_t in0, int64_t in1, void* out, int64_t z0,
                       int64_t z1)>
         apply;
+    // the same with a second input (run_pipeline's in2): slab2 holds the planes [in0, in1) of
+    // the second array, whole planes of the first array's shape in the second array's type
+    std::function<int(zt_ctx*, const void* slab, const void* slab2, int64_t in0, int64_t in1,
+                      void* out, int64_t z0, int64_t z1)>
+        apply2;
 };
 
+// With a second input `in2` of the same shape (any type, chunk grid and codecs; no axis-1 window):
+// rows stay the first array's; every ring slot also holds a pinned row of in2 of the same shape,
+// into which the chunks of in2 that meet the row's planes are decoded (read_chunk clips to it, so a
+// chunk of in2 taller than a row is decoded once per row it meets, as in run_reduce_pipeline);
+// every device slot holds a second slab, copied plane range by plane range like the first, and
+// op.apply2 runs instead of op.apply. The budgets and --chunk-limit count both inputs.
 void run_pipeline(const Array& in, const Array& out, int device, int64_t row_begin,
                   int64_t row_end, int nthreads, const RowOp& op, zt_store_stats* st,
-                  const ColWin* cw = nullptr) {
+                  const ColWin* cw = nullptr, const Array* in2 = nullptr) {
     const auto t_start = Clock::now();
     const int nd = in.ndim();
     const bool elide = g_store_empty_chunks == 0;  // store_empty_chunks = false
@@ -637,6 +655,13 @@ void run_pipeline(const Array& in, const Array& out, int device, int64_t row_beg
     const int64_t oc0 = cw ? cw->o0 / out.chunk_shape[1] : 0;
     const int64_t oc1 = cw ? (cw->o1 + out.chunk_shape[1] - 1) / out.chunk_shape[1] : -1;
     const size_t in_pb = (size_t)in_plane * in.esz, out_pb = (size_t)out_plane * out.esz;
+    const size_t in2_pb = in2 ? (size_t)in_plane * in2->esz : 0;
+    // the chunk rows of in2 that meet row j of `in`
+    auto rows2 = [&](int64_t j, int64_t& r0, int64_t& r1) {
+        const int64_t cz2 = in2->chunk_shape[0];
+        r0 = j * in_cz / cz2;
+        r1 = (std::min((j + 1) * in_cz, nz_in) + cz2 - 1) / cz2;
+    };
 
     // input row span of each output row, and the largest slab
     auto span = [&](int64_t k, int64_t& in0, int64_t& in1, int64_t& j0, int64_t& j1) {
@@ -653,7 +678,9 @@ void run_pipeline(const Array& in, const Array& out, int device, int64_t row_beg
         max_rows_per = std::max(max_rows_per, j1 - j0 + 1);
     }
     // memory budget: ring depth NR (rows decoded ahead) and NB (double-buffered slabs / outputs)
-    const uint64_t in_row_b = (uint64_t)in_cz * in_pb, out_row_b = (uint64_t)out_cz * out_pb;
+    // (with a second input, a row of each)
+    const uint64_t in_row_b = (uint64_t)in_cz * (in_pb + in2_pb);
+    const uint64_t out_row_b = (uint64_t)out_cz * out_pb;
     const uint64_t host_budget = host_available_bytes() / 10 * 8;
     int64_t NR = max_rows_per + 2;  // ring of decoded input rows (+1 decoding ahead, +1 slack)
     int NB = 2;
@@ -665,7 +692,17 @@ void run_pipeline(const Array& in, const Array& out, int device, int64_t row_beg
     // --chunk-limit: the chunks held in flight (decoded input rows + output rows being computed
     // or encoded) stay within the limit, down to the pipeline's unit of one slab and one output
     // row without overlap (a chunk row is the device's unit of work)
-    const int64_t in_row_chunks = (int64_t)chunks_in_rows(in, 0, 1, ic0, ic1).size();
+    int64_t in_row_chunks = (int64_t)chunks_in_rows(in, 0, 1, ic0, ic1).size();
+    if (in2) {  // the most chunks of in2 decoded for one row
+        const int64_t per2 = (int64_t)chunks_in_rows(*in2, 0, 1).size();
+        int64_t most = 0;
+        for (int64_t j = 0; j * in_cz < nz_in; ++j) {
+            int64_t r0, r1;
+            rows2(j, r0, r1);
+            most = std::max(most, r1 - r0);
+        }
+        in_row_chunks += most * per2;
+    }
     const int64_t out_row_chunks = (int64_t)chunks_in_rows(out, 0, 1, oc0, oc1).size();
     int threads = resolve_threads(nthreads);
     if (g_chunk_limit > 0) {
@@ -683,7 +720,7 @@ void run_pipeline(const Array& in, const Array& out, int device, int64_t row_beg
         const uint64_t scratch = op.scratch_bytes ? op.scratch_bytes(max_slab) : 0;
         const uint64_t dev_budget = device_available_bytes() / 10 * 8;
         auto dev_need = [&](int nb) {
-            return (uint64_t)nb * ((uint64_t)max_slab * in_pb + out_row_b) + scratch;
+            return (uint64_t)nb * ((uint64_t)max_slab * (in_pb + in2_pb) + out_row_b) + scratch;
         };
         if (dev_need(NB) > dev_budget) NB = 1;
         if (dev_need(NB) > dev_budget) throw zt::zarr::Error(ZT_ERR_OUT_OF_MEMORY, kNotEnoughMemory);
@@ -703,13 +740,15 @@ void run_pipeline(const Array& in, const Array& out, int device, int64_t row_beg
     std::vector<bool> ring_ev_set(NR, false);
     for (auto& e : ring_ev) e = E.make();
 
-    std::vector<Pinned> hin(NR);
+    std::vector<Pinned> hin(NR), hin2(in2 ? NR : 0);
     for (auto& h : hin) h.alloc((size_t)in_cz * in_pb);
+    for (auto& h : hin2) h.alloc((size_t)in_cz * in2_pb);
     Pinned hout[2];
     for (int s = 0; s < NB; ++s) hout[s].alloc((size_t)out_cz * out_pb);
-    DevBuf dslab[2], dout[2];
+    DevBuf dslab[2], dslab2[2], dout[2];
     for (int s = 0; s < NB; ++s) {
         dslab[s].alloc((size_t)max_slab * in_pb);
+        if (in2) dslab2[s].alloc((size_t)max_slab * in2_pb);
         dout[s].alloc((size_t)out_cz * out_pb);
     }
 
@@ -776,6 +815,21 @@ void run_pipeline(const Array& in, const Array& out, int device, int64_t row_beg
                 if (cw) origin[1] = cw->i0;
                 size_t n = in.read_chunk(idx.data(), buf, origin.data(), in_row_shape.data(),
                                          in_row_st.data());
+                bytes_read += n;
+                dec_ns += (int64_t)(secs_since(t0) * 1e9);
+            });
+        }
+        if (!in2) return;
+        int64_t r0, r1;
+        rows2(j, r0, r1);
+        uint8_t* buf2 = hin2[s].u8();
+        for (auto& idx : chunks_in_rows(*in2, r0, r1)) {
+            pool.submit(dec_group[s], [&, idx, buf2, j] {
+                const auto t0 = Clock::now();
+                std::vector<int64_t> origin(nd, 0);
+                origin[0] = j * in_cz;
+                size_t n = in2->read_chunk(idx.data(), buf2, origin.data(), in_row_shape.data(),
+                                           in_row_st.data());
                 bytes_read += n;
                 dec_ns += (int64_t)(secs_since(t0) * 1e9);
             });
@@ -861,6 +915,11 @@ void run_pipeline(const Array& in, const Array& out, int device, int64_t row_beg
                 HIPCHK(hipMemcpyAsync(dslab[s].u8() + (size_t)(p0 - in0) * in_pb,
                                       hin[j % NR].u8() + (size_t)(p0 - j * in_cz) * in_pb,
                                       (size_t)(p1 - p0) * in_pb, hipMemcpyHostToDevice, s_h2d));
+                if (in2)
+                    HIPCHK(hipMemcpyAsync(dslab2[s].u8() + (size_t)(p0 - in0) * in2_pb,
+                                          hin2[j % NR].u8() + (size_t)(p0 - j * in_cz) * in2_pb,
+                                          (size_t)(p1 - p0) * in2_pb, hipMemcpyHostToDevice,
+                                          s_h2d));
             }
             HIPCHK(hipEventRecord(ev_h2d[s], s_h2d));
             for (int64_t j = j0; j <= j1; ++j) {
@@ -872,8 +931,10 @@ void run_pipeline(const Array& in, const Array& out, int device, int64_t row_beg
             HIPCHK(hipStreamWaitEvent(s_comp, ev_d2h[s], 0));  // D2H k-NB done with dout[s]
             HIPCHK(hipEventRecord(ev_k0[s], s_comp));
             const int64_t z0 = k * out_cz, z1 = std::min(z0 + out_cz, nz_out);
-            if (int rc = op.apply(ctx.c, dslab[s].p, in0, in1, dout[s].p, z0, z1))
-                throw zt::zarr::Error(rc, zt_last_error());
+            const int rc =
+                in2 ? op.apply2(ctx.c, dslab[s].p, dslab2[s].p, in0, in1, dout[s].p, z0, z1)
+                    : op.apply(ctx.c, dslab[s].p, in0, in1, dout[s].p, z0, z1);
+            if (rc) throw zt::zarr::Error(rc, zt_last_error());
             if (elide) {  // the row's real extents, cells of the inner chunk shape
                 std::vector<int64_t> ext(out_row_shape);
                 ext[0] = z1 - z0;
@@ -1217,16 +1278,11 @@ int zt_store_compare(const char* first_path, const char* second_path, int device
         if (stats) *stats = zt_store_stats{};
         Array a = Array::open(first_path), b = Array::open(second_path);
         // shape, then data type (zarrs_validate.rs:101-113): no device work yet
-        if (a.shape != b.shape) {
-            auto list = [](const std::vector<int64_t>& v) {  // `{:?}` of a Vec<u64>
-                std::string s = "[";
-                for (size_t i = 0; i < v.size(); ++i) s += (i ? ", " : "") + std::to_string(v[i]);
-                return s + "]";
-            };
+        if (a.shape != b.shape)
             return zt::set_last_error(
                 ZT_ERR_INVALID_PARAMETERS,
-                ("Array shapes do not match: " + list(a.shape) + " vs " + list(b.shape)).c_str());
-        }
+                ("Array shapes do not match: " + shape_list(a.shape) + " vs " +
+                 shape_list(b.shape)).c_str());
         if (a.dtype != b.dtype)
             return zt::set_last_error(
                 ZT_ERR_INVALID_PARAMETERS,
@@ -1912,6 +1968,46 @@ int zt_store_pointwise(const char* in_path, const char* out_path, int dtype_out,
         bool empty = false;
         for (int d = 0; d < nd; ++d) empty = empty || oshape[d] == 0;
         if (!empty) run_pipeline(in, out, device, row_begin, row_end, nthreads, rop, stats);
+        if (flags & ZT_STORE_FINISH_OUTPUT) out.store_metadata();
+        return ZT_OK;
+    } catch (const std::exception& e) {
+        return report(e);
+    }
+}
+
+int zt_store_arithmetic(const char* first_path, const char* second_path, const char* out_path,
+                        int dtype_out, const char* encoding_json, int op, int device,
+                        int64_t row_begin, int64_t row_end, int nthreads, int flags,
+                        zt_store_stats* stats) {
+    try {
+        if (!first_path || !second_path || !out_path)
+            return zt::set_last_error(ZT_ERR_INVALID_PARAMETERS, "null argument");
+        if (stats) *stats = zt_store_stats{};
+        Array a = Array::open(first_path), b = Array::open(second_path);
+        if (a.shape != b.shape)  // the wording of zt_store_compare; no device work yet
+            return zt::set_last_error(
+                ZT_ERR_INVALID_PARAMETERS,
+                ("Array shapes do not match: " + shape_list(a.shape) + " vs " +
+                 shape_list(b.shape)).c_str());
+        Array out = build_output(a, out_path, dtype_out, a.shape, encoding_json);
+        const int dt = out.dtype, dta = a.dtype, dtb = b.dtype;
+        if (int rc = zt_arithmetic_is_compatible(op, dta, dtb, dt)) return rc;
+        if (flags & ZT_STORE_ERASE_OUTPUT_METADATA) out.erase_metadata();
+        int64_t plane = 1;
+        for (int d = 1; d < a.ndim(); ++d) plane *= a.shape[d];
+        RowOp rop;
+        rop.input_planes = [&](int64_t z0, int64_t z1, int64_t& p0, int64_t& p1) {
+            p0 = z0;  // no halo
+            p1 = z1;
+        };
+        rop.apply2 = [&](zt_ctx* c, const void* sa, const void* sb, int64_t, int64_t, void* o,
+                         int64_t z0, int64_t z1) -> int {
+            return zt_arithmetic_apply(c, op, dta, sa, dtb, sb, (z1 - z0) * plane, dt, o);
+        };
+        bool empty = false;
+        for (int d = 0; d < a.ndim(); ++d) empty = empty || a.shape[d] == 0;
+        if (!empty)
+            run_pipeline(a, out, device, row_begin, row_end, nthreads, rop, stats, nullptr, &b);
         if (flags & ZT_STORE_FINISH_OUTPUT) out.store_metadata();
         return ZT_OK;
     } catch (const std::exception& e) {

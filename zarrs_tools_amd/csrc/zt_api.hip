@@ -1522,6 +1522,46 @@ int zt_pointwise_apply_ndarray(zt_ctx* ctx, int dtype_in, const void* in, const 
     return ZT_OK;
 }
 
+// ---- two-array arithmetic (an extension; arithmetic.hip) ----------------------------------------
+
+int zt_arithmetic_is_compatible(int op, int dtype_a, int dtype_b, int dtype_out) {
+    if (op < ZT_AR_ADD || op > ZT_AR_ABSOLUTE_DIFFERENCE)
+        return fail(ZT_ERR_INVALID_PARAMETERS, "unknown arithmetic operator %d", op);
+    for (int d : {dtype_a, dtype_b, dtype_out})
+        if (!valid_dtype(d))
+            return fail(ZT_ERR_UNSUPPORTED_DATA_TYPE, "Unsupported data type code %d", d);
+    return ZT_OK;
+}
+
+int zt_arithmetic_memory_per_chunk(int op, int dtype_a, int dtype_b, int dtype_out,
+                                   const int64_t* chunk_shape, int ndim, uint64_t* bytes) {
+    if (int rc = zt_arithmetic_is_compatible(op, dtype_a, dtype_b, dtype_out)) return rc;
+    if (int rc = check_shape(chunk_shape, ndim, "chunk_shape")) return rc;
+    if (!bytes) return fail(ZT_ERR_INVALID_PARAMETERS, "null pointer");
+    *bytes = (uint64_t)numel(chunk_shape, ndim) *
+             (zt::dtype_size(dtype_a) + zt::dtype_size(dtype_b) + zt::dtype_size(dtype_out));
+    return ZT_OK;
+}
+
+int zt_arithmetic_apply(zt_ctx* ctx, int op, int dtype_a, const void* a, int dtype_b,
+                        const void* b, int64_t n, int dtype_out, void* out) {
+    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = zt_arithmetic_is_compatible(op, dtype_a, dtype_b, dtype_out)) return rc;
+    if (n < 0) return fail(ZT_ERR_INVALID_PARAMETERS, "negative element count");
+    if (n == 0) return ZT_OK;
+    if (!a || !b || !out) return fail(ZT_ERR_INVALID_PARAMETERS, "null data pointer");
+    if (((uintptr_t)a % zt::dtype_size(dtype_a)) != 0 ||
+        ((uintptr_t)b % zt::dtype_size(dtype_b)) != 0 ||
+        ((uintptr_t)out % zt::dtype_size(dtype_out)) != 0)
+        return fail(ZT_ERR_INVALID_PARAMETERS, "data pointers must be element aligned");
+    DeviceGuard guard(ctx->device);
+    if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev0, ctx->cur));
+    hipError_t e = zt::launch_arithmetic(a, dtype_a, b, dtype_b, out, dtype_out, n, op, ctx->cur);
+    if (e != hipSuccess) return hip_fail(e, "arithmetic launch");
+    if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev1, ctx->cur));
+    return ZT_OK;
+}
+
 // ---- zarrs_info reductions (range.rs, histogram.rs) --------------------------------------------
 
 namespace {

@@ -237,6 +237,20 @@ int pointwise_max_blocks();
 hipError_t launch_pointwise(const void* in, void* out, PwGeom g, const PwProgram& prog,
                             hipStream_t s);
 
+// Two-array arithmetic (arithmetic.hip; an extension, no reference filter): out[i] =
+// (a[i] as f64 op b[i] as f64) as dt_out over n contiguous elements; the three pointers need
+// element alignment only and `out` must not overlap a or b. A workgroup step is kArStepElems
+// elements.
+enum ArOp : int {
+    kArAdd = 0, kArSubtract = 1, kArMultiply = 2, kArDivide = 3, kArMinimum = 4, kArMaximum = 5,
+    kArAbsoluteDifference = 6, kArOps = 7
+};
+constexpr int kArThreads = 256;
+constexpr int kArStepElems = 4096;
+int arithmetic_max_blocks();
+hipError_t launch_arithmetic(const void* a, int dt_a, const void* b, int dt_b, void* out,
+                             int dt_out, int64_t n, int op, hipStream_t s);
+
 // zarrs_info reductions (info.hip; src/info/range.rs, src/info/histogram.rs) over a contiguous
 // run of n elements of `dtype` (the 12 numeric types) at element alignment.
 // Range: `state` is two device u64 words (smallest key, largest key) that accumulate across

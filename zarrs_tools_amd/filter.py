@@ -21,6 +21,8 @@ Names, argument meaning and error behaviour follow LDeakin/zarrs_tools 0.7.2:
     reductions; ``combine_ranges`` / ``combine_histograms`` join partial results)
   - ``Compare`` <- src/bin/zarrs_validate.rs:145-147 (the bitwise comparison of two arrays;
     ``combine_compares`` joins partial results)
+  - ``Arithmetic``: an extension with no counterpart in the reference (two arrays in, one out);
+    its semantics are DESIGN.md §3.12
   - ``chunk_occupancy`` <- zarrs' ``store_empty_chunks = false`` (which chunks of a device
     array hold anything but the fill value)
   - ``ArraySubsetOverlap`` <- src/filter/array_subset_overlap.rs:4-52
@@ -1233,6 +1235,78 @@ class Compare:
         check(lib().zt_compare_accumulate(ctx.handle, _info_dtype(dtype), _ptr(x), _ptr(y),
                                           x.numel(), 0, _ptr(state)))
         return self.finish(state, ctx)
+
+
+ARITHMETIC_OPERATORS = tuple(_abi.AR_OPERATORS)
+
+
+def arithmetic_operator(operator) -> int:
+    """The ZT_AR_* code of an operator name (hyphens or underscores)."""
+    key = str(operator).replace("-", "_")
+    if key not in _abi.AR_OPERATORS:
+        raise _invalid(f"arithmetic: unknown operator {operator!r} "
+                       f"(one of {', '.join(ARITHMETIC_OPERATORS)})")
+    return _abi.AR_OPERATORS[key]
+
+
+class Arithmetic:
+    """An extension with no counterpart in the reference: out = (first as f64
+    `operator` second as f64) as TOut, element by element, for two arrays of one shape. All 13
+    types for each of the three arrays; the default output type is the first array's."""
+
+    def __init__(self, operator: str, chunk_limit: Optional[int] = None):
+        self.op = arithmetic_operator(operator)
+        self.operator = str(operator).replace("-", "_")
+        self.chunk_limit = chunk_limit
+
+    def name(self) -> str:
+        return "arithmetic"
+
+    def is_compatible(self, dtype_a: str, dtype_b: str, dtype_out: str) -> None:
+        codes = [_info_dtype(d) for d in (dtype_a, dtype_b, dtype_out)]
+        check(lib().zt_arithmetic_is_compatible(self.op, *codes))
+
+    def memory_per_chunk(self, dtype_a: str, dtype_b: str, dtype_out: str, chunk_shape) -> int:
+        out = ctypes.c_uint64()
+        check(lib().zt_arithmetic_memory_per_chunk(
+            self.op, DTYPES[dtype_a], DTYPES[dtype_b], DTYPES[dtype_out], i64_array(chunk_shape),
+            len(chunk_shape), ctypes.byref(out)))
+        return int(out.value)
+
+    def _run(self, x, dtype_a, y, dtype_b, out, dtype_out, ctx) -> None:
+        if tuple(x.shape) != tuple(y.shape):
+            raise _invalid(f"Array shapes do not match: {list(x.shape)} vs {list(y.shape)}")
+        if tuple(out.shape) != tuple(x.shape):
+            raise _invalid(f"Array shapes do not match: {list(x.shape)} vs {list(out.shape)}")
+        if x.device != y.device or x.device != out.device:
+            raise _invalid("arithmetic: the arrays are on different devices")
+        if not out.is_contiguous():
+            raise _invalid("arithmetic: the output must be contiguous")
+        self.is_compatible(dtype_a, dtype_b, dtype_out)
+        ctx = ctx or default_context(x.device.index)
+        check(lib().zt_arithmetic_apply(ctx.handle, self.op, DTYPES[dtype_a], _ptr(x),
+                                        DTYPES[dtype_b], _ptr(y), x.numel(), DTYPES[dtype_out],
+                                        _ptr(out)))
+
+    def apply_ndarray(self, a, b, dtype_out: Optional[str] = None, ctx: Optional[Context] = None,
+                      out=None):
+        """first `operator` second on two device tensors of one shape; returns a new tensor of
+        `dtype_out` (default: the first's type), or fills and returns `out` (contiguous, of
+        `dtype_out`, not overlapping an input)."""
+        x, dtype_a = _info_run(a)
+        y, dtype_b = _info_run(b)
+        dtype_out = dtype_out or (dtype_of(out) if out is not None else dtype_a)
+        if out is None:
+            out = _torch().empty(tuple(x.shape), dtype=torch_dtype(dtype_out), device=x.device)
+        self._run(x, dtype_a, y, dtype_b, out, dtype_out, ctx)
+        return out
+
+    def apply(self, first: DeviceArray, second: DeviceArray, output: DeviceArray,
+              ctx: Optional[Context] = None) -> None:
+        """The filter's `apply` over device-resident arrays: one launch."""
+        x, dtype_a = _info_run(first)
+        y, dtype_b = _info_run(second)
+        self._run(x, dtype_a, y, dtype_b, output.data, output.dtype, ctx)
 
 
 class Downsample:

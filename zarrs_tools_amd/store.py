@@ -431,6 +431,23 @@ def rank_filter(input_path, output_path, kind: str, kernel_half_size,
     return _stats(st)
 
 
+def arithmetic(first, second, output, operator: str, data_type: Optional[str] = None,
+               device: int = 0, rows=None, nthreads: int = 0, erase: bool = True,
+               finish: bool = True, encoding=None, chunk_limit: int = 0) -> dict:
+    """zarrs_filter arithmetic FIRST OUTPUT OPERATOR SECOND [--data-type T]: output = first
+    `operator` second, element by element (filter.Arithmetic); the output array is built from the
+    first array. `operator`: one of filter.ARITHMETIC_OPERATORS."""
+    from .filter import arithmetic_operator
+    op = arithmetic_operator(operator)
+    set_chunk_limit(chunk_limit)
+    st = _abi.StoreStats()
+    r0, r1 = (0, -1) if rows is None else (int(rows[0]), int(rows[1]))
+    check(lib().zt_store_arithmetic(_b(first), _b(second), _b(output), _dt(data_type),
+                                    _enc(encoding), op, int(device), r0, r1, int(nthreads),
+                                    _flags(erase, finish), ctypes.byref(st)))
+    return _stats(st)
+
+
 def summed_area_table(input_path, output_path, data_type: Optional[str] = None, device: int = 0,
                       nthreads: int = 0, erase: bool = True, finish: bool = True, encoding=None,
                       chunk_limit: int = 0) -> dict:

@@ -1,6 +1,6 @@
 """``zarrs_filter`` for the on-path filters (guided_filter, downsample, gaussian,
-summed_area_table, the rank filters median, minimum, maximum and the per-element reencode, crop,
-rescale, clamp, equal, replace_value) over Zarr V3 stores.
+summed_area_table, the rank filters median, minimum, maximum, the per-element reencode, crop,
+rescale, clamp, equal, replace_value and the two-array arithmetic) over Zarr V3 stores.
 
 Mirrors src/bin/zarrs_filter.rs (LDeakin/zarrs_tools 0.7.2) for the filters this framework
 accelerates:
@@ -16,7 +16,8 @@ accelerates:
                                         | reencode IN OUT | crop IN OUT OFFSET SHAPE
                                         | rescale IN OUT MULTIPLY ADD [--add-first]
                                         | clamp IN OUT MIN MAX | equal IN OUT VALUE
-                                        | replace-value IN OUT VALUE REPLACE]
+                                        | replace-value IN OUT VALUE REPLACE
+                                        | arithmetic IN OUT OPERATOR OTHER [--data-type T]]
 
 * subcommand arguments as GuidedFilterArguments (guided_filter.rs:25-33),
   DownsampleArguments (downsample.rs:20-33, STRIDE comma delimited) and GaussianArguments
@@ -29,11 +30,16 @@ accelerates:
   (clamp.rs:20-25), EqualArguments (equal.rs:23-34) and ReplaceValueArguments
   (replace_value.rs:23-44); VALUE and REPLACE follow parse_fill_value (a JSON number, true /
   false, NaN, Infinity, -Infinity) and negative numbers parse as values;
+  arithmetic (an extension: the reference has no two-array filter) writes
+  OUT = IN OPERATOR OTHER element by element, OPERATOR one of add, subtract, multiply, divide,
+  minimum, maximum, absolute-difference (hyphens on the command line, snake_case in a run
+  config), OTHER a second array of IN's shape and of any type, chunk grid and codecs;
 * a JSON run config is a list of {"filter": "guided_filter" | "downsample" | "gaussian" |
   "summed_area_table" | "median" | "minimum" | "maximum" | "reencode" | "crop" | "rescale" |
-  "clamp" | "equal" | "replace_value", "input", "output", ...args (kernel_half_size; offset, shape, multiply, add, add_first, min, max, value, replace
-  for the per-element filters), "data_type"}, with "$name" meaning a named temporary array
-  under --tmp and an omitted input meaning the previous filter's output (zarrs_filter.rs:106-138,
+  "clamp" | "equal" | "replace_value" | "arithmetic", "input", "output", ...args (kernel_half_size; offset, shape, multiply, add, add_first, min, max, value, replace
+  for the per-element filters; operator, other for arithmetic, whose "other" is a path or the
+  "$name" of a temporary that an earlier step wrote), "data_type"}, with "$name" meaning a named
+  temporary array under --tmp and an omitted input meaning the previous filter's output (zarrs_filter.rs:106-138,
   :338-381);
 * a chain of steps linked only through temporaries (a "$name" or implicit output read by the
   next step alone) runs device-resident when its arrays fit 80 % of the free device memory: the
@@ -42,7 +48,9 @@ accelerates:
   chunks never go through the store (`--no-device-chain` forces the store path); inside such a
   chain a run of consecutive per-element steps is one kernel launch that reads each element once
   and writes it once (up to 8 steps per launch; crops compose by adding their offsets;
-  `--no-pointwise-fusion` launches them one by one);
+  `--no-pointwise-fusion` launches them one by one); an arithmetic step is never part of such
+  a chain (it runs store -> store and ends the chain before it), and a temporary that a later
+  arithmetic step reads as its "other" is written to the store by the step that produces it;
 * every filter takes the reencoding arguments (ZarrReencodingArgs, lib.rs:274-377: -d/--data-type,
   -f/--fill-value, --separator, -c/--chunk-shape, -s/--shard-shape, --array-to-array-codecs,
   --array-to-bytes-codec, --bytes-to-bytes-codecs, --dimension-names, --attributes,
@@ -82,7 +90,9 @@ from . import store as S
 
 POINTWISE = ("reencode", "crop", "rescale", "clamp", "equal", "replace_value")
 RANK = ("median", "minimum", "maximum")
-ON_PATH = ("guided_filter", "downsample", "gaussian", "summed_area_table") + RANK + POINTWISE
+BINARY = ("arithmetic",)  # two arrays in: "input" and "other"
+ON_PATH = ("guided_filter", "downsample", "gaussian", "summed_area_table") + RANK + POINTWISE + \
+    BINARY
 
 
 def rows_splittable(name: str) -> bool:
@@ -250,6 +260,12 @@ def build_parser() -> argparse.ArgumentParser:
     rv.add_argument("value", type=_parse_fill_value)
     rv.add_argument("replace", type=_parse_fill_value)
     _add_reencode_args(rv)
+    ar = sub.add_parser("arithmetic", help="Combine two arrays of one shape element by element.")
+    ar.add_argument("input")
+    ar.add_argument("output")
+    ar.add_argument("operator", choices=[o.replace("_", "-") for o in _abi.AR_OPERATORS])
+    ar.add_argument("other")
+    _add_reencode_args(ar)
     return ap
 
 
@@ -281,6 +297,11 @@ def _steps_from_cli(a) -> list:
         return [{"filter": a.filter.replace("-", "_"), "input": a.input, "output": a.output,
                  **{k: getattr(a, k) for k in own[a.filter]}, "data_type": a.data_type,
                  "chunk_limit": a.filter_chunk_limit, **_reencode_of(a)}]
+    if a.filter == "arithmetic":
+        return [{"filter": "arithmetic", "input": a.input, "output": a.output,
+                 "operator": a.operator.replace("-", "_"), "other": a.other,
+                 "data_type": a.data_type, "chunk_limit": a.filter_chunk_limit,
+                 **_reencode_of(a)}]
     return []
 
 
@@ -291,15 +312,18 @@ def _is_temp(p) -> bool:
 def plan_chains(steps: list) -> list:
     """Maximal runs [i, j] of steps (j > i) where every step before j hands its output to the next
     step only: the output is a temporary (a "$name", or omitted) and the next step reads it (its
-    input is that "$name", or omitted = the previous output), and no other step names it."""
+    input is that "$name", or omitted = the previous output), and no other step names it, as
+    its input, output or (arithmetic) "other". An arithmetic step is never part of a chain."""
     refs: dict = {}
     for st in steps:
-        for key in ("input", "output"):
+        for key in ("input", "output", "other"):
             v = st.get(key)
             if isinstance(v, str) and v.startswith("$"):
                 refs[v] = refs.get(v, 0) + 1
 
     def linked(k):
+        if steps[k].get("filter") in BINARY or steps[k + 1].get("filter") in BINARY:
+            return False
         out, nxt = steps[k].get("output"), steps[k + 1].get("input")
         if not _is_temp(out):
             return False
@@ -353,6 +377,17 @@ def pointwise_filter(step: dict):
     raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS, f"{name} is not a per-element filter")
 
 
+def arithmetic_args(step: dict):
+    """(operator, other) of an arithmetic run-config step."""
+    from .filter import arithmetic_operator
+    missing = [k for k in ("operator", "other") if step.get(k) is None]
+    if missing:
+        raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS,
+                                     f"arithmetic needs {', '.join(missing)}")
+    arithmetic_operator(step["operator"])  # InvalidParameters for an unknown name
+    return str(step["operator"]).replace("-", "_"), step["other"]
+
+
 def step_encoding(step: dict, in_data_type: str):
     """The reencoding a step's output array is created with: encoding_of(step), and for a
     per-element filter that sets its own output type (equal: bool, fill value false) that type
@@ -392,6 +427,8 @@ def _step_params(step, info):
         return F.Gaussian(sigma, half), tuple(info.shape), dt
     if name == "summed_area_table":
         return F.SummedAreaTable(), tuple(info.shape), dt
+    if name == "arithmetic":
+        return F.Arithmetic(arithmetic_args(step)[0]), tuple(info.shape), dt
     if name in RANK:
         half = step.get("kernel_half_size")
         half = _parse_stride(half) if isinstance(half, str) else half
@@ -713,6 +750,8 @@ def _rows_worker(name: str, src: str, dst: str, params: dict, device: int, rows,
         return S.rank_filter(src, dst, name, params["kernel_half_size"], **kw)
     if name in POINTWISE:
         return _store_pointwise(name, src, dst, params["args"], **kw)
+    if name == "arithmetic":
+        return S.arithmetic(src, params["other"], dst, params["operator"], **kw)
     if name == "downsample_gaussian":  # a zarrs_ome level with --gaussian-sigma
         return S.downsample_gaussian(src, dst, params["stride"], params["sigma"],
                                      params["kernel_half_size"], **kw)
@@ -878,6 +917,13 @@ def run(steps: list, exists: str = "erase", tmp: str | None = None,
             log(f"{i}: {name} {params['args']} {src} ({info.data_type} {list(info.shape)}) "
                 f"-> {dst}")
             enc = step_encoding(step, info.data_type)  # equal: bool, fill value false
+        elif name == "arithmetic":
+            other = step["other"]
+            if isinstance(other, str) and other.startswith("$"):
+                other = temps[other]  # written by an earlier step (checked before the run)
+            params = {"operator": f.operator, "other": str(other)}
+            log(f"{i}: arithmetic {f.operator} {src} ({info.data_type} {list(info.shape)}) "
+                f"with {other} -> {dst}")
         else:
             params = {"stride": list(f.stride), "discrete": bool(step.get("discrete", False))}
             log(f"{i}: downsample stride={params['stride']} discrete={params['discrete']} "
@@ -910,6 +956,10 @@ def run(steps: list, exists: str = "erase", tmp: str | None = None,
         elif name in POINTWISE:
             st = _store_pointwise(name, src, dst, params["args"], data_type=params["data_type"],
                                   device=device, encoding=enc, chunk_limit=limit)
+        elif name == "arithmetic":
+            st = S.arithmetic(src, params["other"], dst, params["operator"],
+                              data_type=params["data_type"], device=device, encoding=enc,
+                              chunk_limit=limit)
         else:
             st = S.downsample(src, dst, params["stride"], discrete=params["discrete"],
                               data_type=params["data_type"], device=device, encoding=enc,
@@ -927,6 +977,17 @@ def run(steps: list, exists: str = "erase", tmp: str | None = None,
             raise _abi.FilterError(_abi.ERR_OTHER,
                                    f"filter {name!r} is outside the accelerated path "
                                    f"(supported: {', '.join(ON_PATH)})")
+    written = set()  # the temporaries that the steps so far write
+    for step in steps:
+        if step.get("filter") in BINARY:
+            other = arithmetic_args(step)[1]
+            if isinstance(other, str) and other.startswith("$") and other not in written:
+                raise _abi.InvalidParameters(
+                    _abi.ERR_INVALID_PARAMETERS,
+                    f"arithmetic: other {other} is not the output of an earlier step")
+        out = step.get("output")
+        if isinstance(out, str) and out.startswith("$"):
+            written.add(out)
     chains = dict(plan_chains(steps)) if device_chain and _device_ok(device) else {}
     t_all = time.perf_counter()
     if sys.stderr.isatty():
