@@ -49,8 +49,23 @@
 #ifndef GF_P1PFD
 #define GF_P1PFD 2  // stage-1 slices prefetched this many steps ahead at r = 4 (1 or 2)
 #endif
+#ifndef GF_P1PFD_R4M1
+#define GF_P1PFD_R4M1 1  // the same at r = 4 in mode 1: one step, its second buffer's 8 VGPRs go to
+                         // GF_CNTREG and GF_P3VPF (profiles/gf_counts_p3v_ab.txt)
+#endif
 #ifndef GF_P1PFD_R2
 #define GF_P1PFD_R2 2  // the same at r <= 2 (stage-1 ring: entering quads only)
+#endif
+#ifndef GF_CNTREG
+#define GF_CNTREG 1  // r = 4, mode 1: window counts, reciprocals and masks held per lane, refreshed
+                     // only in unrolled blocks with a clamped z (0: recomputed every step; 10 VGPRs)
+#endif
+#ifndef GF_P3VPF
+#define GF_P3VPF 2  // r = 4, mode 1: P3's v loaded this many steps ahead (1 or 2; 4 VGPRs)
+#endif
+#ifndef GF_P5VPF
+#define GF_P5VPF 1  // r = 4, mode 1: P5's v loaded this many steps ahead (1 or 2; 2 VGPRs; 2 spills
+                    // SGPRs and measured +4 % beside the two above)
 #endif
 #ifndef GF_WAVE_SKIP
 #define GF_WAVE_SKIP 1  // P4: idle waves branch around the phase
@@ -491,14 +506,15 @@ __device__ __forceinline__ void store_quad_masked(const float (&v)[4], rsrc_t r,
 // The fused kernel.
 //
 // Software-pipelined phases, two LDS barriers per z-step. Iteration `i` runs
-//   C0: P3(i)  [U -> a,b on the E1 apron]  +  P1(i+1) [z-window of v]  +  P5(i-1) [y-sums,
-//       z-blocks, out(i-1-R) -> Lout]
-//   C1: P4(i)  [x-sums of (a,b)]  +  P2(i+1) [x-sums of the v z-window]  +  staging: Lout ->
-//       global (16-B stores), v of slice i+1 -> Lc (P3's input), v of slice i-R -> Lv5 (P5's)
-// with separate LDS buffers per hand-off, so each barrier interval holds independent work from
-// different slices. Every global access is a 16-byte-per-lane quad (4 consecutive x) in
-// interior tiles: the kernel is bound by vector-memory instruction issue otherwise (one dword
-// per lane cost about as much as the whole pointwise stage).
+//   C0: P3(i)  [y-sums of Hx -> U; a,b on the E1 apron -> Lab]  +  P5(i-1) [y-sums of Hab,
+//       z-blocks, out(i-1-R) stored straight to global memory, one dword per lane and row]
+//   C1: the global loads of later steps (the stage-1 quads of P12, and P3's / P5's v: one dword
+//       per lane and row, straight into registers)  +  P12(i+1) [z-window of v in registers,
+//       x-sums by DPP -> Hx]  +  P4(i) [x-sums of (a,b): Lab -> Hab]
+// with separate LDS buffers per hand-off (Hx, Lab, Hab), so each barrier interval holds
+// independent work from different slices. No global value is staged through LDS. The stage-1
+// loads are 16-byte-per-lane quads (4 consecutive x) outside the masked edge mode: with one
+// dword per lane there, the kernel is bound by vector-memory instruction issue.
 // ---------------------------------------------------------------------------------------------
 template <int R, int TY, int NT, int HXB = 8>
 struct GFConfig {
@@ -742,13 +758,44 @@ __global__ __launch_bounds__(NT) void gf3d_fused_kernel(GFParams p) {
     // Two steps ahead at r = 4 and r <= 2 (profiles/r05_p1_prefetch2*.txt: r = 4 f32 -5 % on a
     // box where the march took 30 ms, neutral on a 28.7 ms box, u16 -1 to -3 %; r = 1, 2 -1 to
     // -3.6 %); one step elsewhere (r = 3 / 5 measured +0.5-0.9 %; r > 5 and the masked edge mode
-    // spill the second buffer).
-    constexpr int PF = EDGE ? 1 : R == 4 ? GF_P1PFD : R <= 2 ? GF_P1PFD_R2 : 1;
+    // spill the second buffer). Mode 1 at r = 4 (the headline) gives the second buffer up again:
+    // its registers hold the window counts (CNTREG) and P3's v two steps ahead, which together
+    // measured -3.6 to -6.5 % there, where either alone or beside the second stage-1 buffer
+    // (spills) measured neutral (profiles/gf_counts_p3v_ab.txt).
+    constexpr bool R4M1 = C::R4 && MODE == 1;
+    constexpr int PF = EDGE ? 1 : R4M1 ? GF_P1PFD_R4M1 : R == 4 ? GF_P1PFD : R <= 2 ? GF_P1PFD_R2 : 1;
     SI pa[PF][C::NQP1][EPL], ps[PF][C::NQP1][EPL];
-    float vc[C::K3];  // v of the next P3 slice at this thread's item (prefetched)
-    float v5[K5];     // v of the next P5 output slice at this thread's outputs
+    // P3's and P5's v, loaded PF3 / PF5 steps ahead (buffer b feeds the unrolled steps k with
+    // k % PF3 / PF5 == b). P3's two steps ahead at r = 4 in mode 1.
+    constexpr int PF3 = R4M1 ? GF_P3VPF : 1, PF5 = R4M1 ? GF_P5VPF : 1;
+    static_assert(PF <= 2 && PF3 <= 2 && PF5 <= 2, "the unroll covers one or two windows");
+    float vc[PF3][C::K3];  // v of the next P3 slices at this thread's item (prefetched)
+    float v5[PF5][K5];     // v of the next P5 output slices at this thread's outputs
 #pragma unroll
-    for (int j = 0; j < K5; ++j) v5[j] = 0.0f;
+    for (int b = 0; b < PF5; ++b)
+#pragma unroll
+        for (int j = 0; j < K5; ++j) v5[b][j] = 0.0f;
+    // Window counts of mode 1 at r = 4, held per lane. The x and y counts and the in-domain
+    // masks are constants of the march, and the z count is 2R + 1 except in the first and last R
+    // slices of the array: fc3 / rc3 (P3: count and RN(1 / count) of its K3 rows), rc5 (P5) and
+    // ok3 (P3's rows inside the domain in x and y) are refreshed by refresh_counts only where
+    // the z count changes (see the march).
+    constexpr bool CNTREG = R4M1 && GF_CNTREG;
+    constexpr int NP3 = C::K3 / 2;
+    f2 fc3[NP3], rc3[NP3];
+    float rc5[K5];
+    bool ok3[C::K3];
+#pragma unroll
+    for (int k = 0; k < NP3; ++k) fc3[k] = rc3[k] = (f2){0.0f, 0.0f};
+#pragma unroll
+    for (int j = 0; j < K5; ++j) rc5[j] = 0.0f;
+    if constexpr (CNTREG) {
+        const int item = tid0 - C::T3;
+        const int gx = x0 - R + item % C::E1X, gy0 = y0 - R + item / C::E1X * C::K3;
+#pragma unroll
+        for (int k = 0; k < C::K3; ++k)
+            ok3[k] = item >= 0 && gx >= 0 && gx < nx && gy0 + k >= 0 && gy0 + k < ny;
+    }
     auto load_p1 = [&](auto bc, rsrc_t ra, rsrc_t rs) {  // entering zc+R, leaving zc-R-1
         constexpr int b = decltype(bc)::value;
 #pragma unroll
@@ -835,7 +882,6 @@ __global__ __launch_bounds__(NT) void gf3d_fused_kernel(GFParams p) {
     // Pointwise stage on NP pairs of E1 positions, packed (both lanes of every op in one issue):
     //   u = RN(RN(U) / c)   (summed_area_table_mean, exact: Markstein with rcp = RN(1/c))
     //   s = (v - u)^2;  a = s / (s + eps);  b = (1 - a) * u          (guided_filter.rs:126-137)
-    constexpr int NP3 = C::K3 / 2;
     auto pointwise = [&](const f2 (&Uf)[NP3], const f2 (&v)[NP3], const f2 (&fc)[NP3],
                          const f2 (&rc)[NP3], f2 (&a)[NP3], f2 (&bb)[NP3]) {
         f2 q[NP3], r[NP3], u[NP3], sq[NP3], den[NP3], y[NP3], e[NP3];
@@ -878,8 +924,9 @@ __global__ __launch_bounds__(NT) void gf3d_fused_kernel(GFParams p) {
 #pragma unroll
         for (int j = 0; j < C::K3 + 2 * R; ++j) vin[j] = src[j * C::PH];
     };
-    auto do_p3 = [&](int tid, int zc, const SA (&vin)[C::K3 + 2 * R]) {
+    auto do_p3 = [&](int tid, int zc, auto vbc, const SA (&vin)[C::K3 + 2 * R]) {
         // y-window (f64) of Hx -> U; a, b -> Lab
+        constexpr int vb = decltype(vbc)::value;  // prefetch buffer of this step's v
         const int item = tid - C::T3;
         if (item < 0) return;
         const int col = item % C::E1X, sg = item / C::E1X;
@@ -890,7 +937,7 @@ __global__ __launch_bounds__(NT) void gf3d_fused_kernel(GFParams p) {
 #pragma unroll
         for (int k = 0; k < NP3; ++k) {
             Uf[k] = (f2){(float)U[2 * k], (float)U[2 * k + 1]};
-            vv[k] = (f2){vc[2 * k], vc[2 * k + 1]};  // v of slice zc, loaded a half-step ago
+            vv[k] = (f2){vc[vb][2 * k], vc[vb][2 * k + 1]};  // v of slice zc, loaded PF3 steps ago
         }
         if constexpr (INTERIOR) {
             // every E1 point of the tile has the full x and y windows: count = W^2 * cz(zc)
@@ -911,6 +958,18 @@ __global__ __launch_bounds__(NT) void gf3d_fused_kernel(GFParams p) {
                 const f2 ab1 = zin ? __builtin_shufflevector(a[k], bb[k], 1, 3) : (f2){0.f, 0.f};
                 if (kRowsWhole || ey < C::E1Y) lab[ey * C::PA + col] = ab0;
                 if (kRowsWhole || ey + 1 < C::E1Y) lab[(ey + 1) * C::PA + col] = ab1;
+            }
+        } else if constexpr (CNTREG) {
+            const bool zin = (unsigned)zc < (unsigned)nz;  // wave-uniform
+            pointwise(Uf, vv, fc3, rc3, a, bb);
+#pragma unroll
+            for (int k = 0; k < NP3; ++k) {
+                const int ey = sg * C::K3 + 2 * k;
+                // zero outside the domain: the clamped window sums of stage 2
+                const bool ok0 = zin && ok3[2 * k], ok1 = zin && ok3[2 * k + 1];
+                if (kRowsWhole || ey < C::E1Y) lab[ey * C::PA + col] = ok0 ? (f2){a[k].x, bb[k].x} : (f2){0.f, 0.f};
+                if (kRowsWhole || ey + 1 < C::E1Y)
+                    lab[(ey + 1) * C::PA + col] = ok1 ? (f2){a[k].y, bb[k].y} : (f2){0.f, 0.f};
             }
         } else {
             const int gx = x0 - R + col;
@@ -976,8 +1035,9 @@ __global__ __launch_bounds__(NT) void gf3d_fused_kernel(GFParams p) {
 #pragma unroll
         for (int j = 0; j < K5 + 2 * R; ++j) vin[j] = src[j * C::PB];
     };
-    auto do_p5 = [&](int tid, int zc, auto slot_c, const f2 (&vin)[K5 + 2 * R]) {
+    auto do_p5 = [&](int tid, int zc, auto slot_c, auto vbc, const f2 (&vin)[K5 + 2 * R]) {
         // y-window -> slice sums; z; out -> global
+        constexpr int vb = decltype(vbc)::value;  // prefetch buffer of this step's v
         const int col5 = tid % TX, seg5 = tid / TX;
         f2 s2[K5];
         core_window_sums<R, K5>(vin, s2);
@@ -1006,6 +1066,9 @@ __global__ __launch_bounds__(NT) void gf3d_fused_kernel(GFParams p) {
             const float r = rcp_tab[W * W * clamped_count(zq, nz, R)];  // wave-uniform
 #pragma unroll
             for (int j = 0; j < K5; ++j) rc[j] = (f2){r, r};
+        } else if constexpr (CNTREG) {
+#pragma unroll
+            for (int j = 0; j < K5; ++j) rc[j] = (f2){rc5[j], rc5[j]};
         } else {
             const int cxz = cmul(clamped_count(ox, nx, R), clamped_count(zq, nz, R));
 #pragma unroll
@@ -1020,7 +1083,7 @@ __global__ __launch_bounds__(NT) void gf3d_fused_kernel(GFParams p) {
         for (int j = 0; j < K5; ++j) {
             const f2 q = AB[j] * rc[j];
             const int oy = oyb + j;
-            const float o = __fadd_rn(__fmul_rn(v5[j], q.x), q.y);  // v*=ma; v+=mb
+            const float o = __fadd_rn(__fmul_rn(v5[vb][j], q.x), q.y);  // v*=ma; v+=mb
             const int off = (ox < ox_end && oy < oy_end)
                                 ? ((oy - p.oy0) * osy + (ox - p.ox0)) * OSZ : kBadOff;
             Buf<TOut>::store(from_f32<TOut>(o), ro5, opaque(off));
@@ -1035,7 +1098,8 @@ __global__ __launch_bounds__(NT) void gf3d_fused_kernel(GFParams p) {
     // kernel); straight-line, it waits for exactly the step-old load it needs.
     // Positions outside the domain either read 0 through the range check or read a neighbour
     // row's value that is never used (P3 zeroes its out-of-domain (a, b); P5's store drops).
-    auto load_p3v = [&](rsrc_t r) {
+    auto load_p3v = [&](auto bc, rsrc_t r) {
+        constexpr int b = decltype(bc)::value;
         const int item = (int)threadIdx.x - C::T3;
         const int col = item % C::E1X, sg = item / C::E1X;
         const int gx = x0 - R + col, gy0 = y0 - R + sg * C::K3;
@@ -1044,25 +1108,65 @@ __global__ __launch_bounds__(NT) void gf3d_fused_kernel(GFParams p) {
             const int gy = gy0 + k;
             bool ok = item >= 0;
             if constexpr (EDGE) ok = ok && (unsigned)gx < (unsigned)nx && (unsigned)gy < (unsigned)ny;
-            vc[k] = Buf<TIn>::load(r, opaque(ok ? (gy * sy + gx) * ESZ : kBadOff));
+            vc[b][k] = Buf<TIn>::load(r, opaque(ok ? (gy * sy + gx) * ESZ : kBadOff));
         }
     };
-    auto load_p5v = [&](rsrc_t r) {
+    auto load_p5v = [&](auto bc, rsrc_t r) {
+        constexpr int b = decltype(bc)::value;
         const int col5 = (int)threadIdx.x % TX, seg5 = (int)threadIdx.x / TX;
         const int ox = x0 + col5, oyb = y0 + seg5 * K5;
 #pragma unroll
         for (int j = 0; j < K5; ++j) {
             const int oy = oyb + j;
             const bool ok = ox < ox_end && oy < oy_end;
-            v5[j] = Buf<TIn>::load(r, opaque(ok ? (oy * sy + ox) * ESZ : kBadOff));
+            v5[b][j] = Buf<TIn>::load(r, opaque(ok ? (oy * sy + ox) * ESZ : kBadOff));
         }
+    };
+
+    // The held counts for P3 slice zc3 and P5 output slice zo5 (LDS and registers only), from
+    // the lane's x and y counts, packed 4 bits each into one register (cpk: P3's cx and K3 cy,
+    // then P5's cx and K5 cy). Lanes and slices outside the domain take the nearest in-domain
+    // count (a valid table index); their values are zeroed or their stores dropped.
+    static_assert(!CNTREG || (W <= 15 && C::K3 + K5 + 2 <= 8), "the packed counts fit 32 bits");
+    int cpk = 0;
+    if constexpr (CNTREG) {
+        const int item = max(tid0 - C::T3, 0);
+        const int gx = min(max(x0 - R + item % C::E1X, 0), nx - 1);
+        const int gy0 = y0 - R + item / C::E1X * C::K3;
+        cpk = clamped_count(gx, nx, R);
+#pragma unroll
+        for (int k = 0; k < C::K3; ++k)
+            cpk |= clamped_count(min(max(gy0 + k, 0), ny - 1), ny, R) << (4 + 4 * k);
+        const int ox = min(x0 + tid0 % TX, nx - 1), oyb = y0 + tid0 / TX * K5;
+        cpk |= clamped_count(ox, nx, R) << (4 + 4 * C::K3);
+#pragma unroll
+        for (int j = 0; j < K5; ++j)
+            cpk |= clamped_count(min(oyb + j, ny - 1), ny, R) << (8 + 4 * C::K3 + 4 * j);
+    }
+    auto refresh_counts = [&](int zc3, int zo5) {
+        const int cz3 = clamped_count(min(max(zc3, 0), nz - 1), nz, R);
+        const int cz5 = clamped_count(min(max(zo5, 0), nz - 1), nz, R);
+        // (hidden from the optimiser, which would hoist the unpacked fields out of the march
+        //  into registers that stay live through it)
+        const int pk = opaque(cpk);
+        auto field = [&](int n) { return (pk >> (4 * n)) & 15; };
+        const int cxz3 = cmul(field(0), cz3);
+#pragma unroll
+        for (int k = 0; k < NP3; ++k) {
+            const int c0 = cmul(field(1 + 2 * k), cxz3), c1 = cmul(field(2 + 2 * k), cxz3);
+            fc3[k] = (f2){(float)c0, (float)c1};
+            rc3[k] = (f2){rcp_tab[c0], rcp_tab[c1]};
+        }
+        const int cxz5 = cmul(field(1 + C::K3), cz5);
+#pragma unroll
+        for (int j = 0; j < K5; ++j) rc5[j] = rcp_tab[cmul(field(2 + C::K3 + j), cxz5)];
     };
 
     // ---- prologue: stage 1 of the first slice up to Hx; prefetch step 1 ---------------------
     using B0 = std::integral_constant<int, 0>;
     using BL = std::integral_constant<int, PF - 1>;
     load_p1(BL{}, slice_rsrc(zc_begin + R), slice_rsrc(zc_begin - R - 1));
-    load_p3v(slice_rsrc(zc_begin));
+    static_for<0, PF3>([&](auto jc) { load_p3v(jc, slice_rsrc(zc_begin + decltype(jc)::value)); });
     do_p12(tid0, std::integral_constant<int, W - 1>{}, BL{});
     load_p1(B0{}, slice_rsrc(zc_begin + 1 + R), slice_rsrc(zc_begin - R));
     if constexpr (PF == 2) load_p1(BL{}, slice_rsrc(zc_begin + 2 + R), slice_rsrc(zc_begin + 1 - R));
@@ -1092,13 +1196,24 @@ __global__ __launch_bounds__(NT) void gf3d_fused_kernel(GFParams p) {
     // from different slices. The step count is padded to a multiple of W, at least one past the
     // last stage-1 slice so that P5 / the store of the last output slice happen inside the loop:
     // no guards inside. Padded steps emit nothing (zo >= zo_end).
-    constexpr int UN = PF * W;  // unrolled steps: every ring slot and prefetch buffer a constant
+    // unrolled steps: every ring slot and prefetch buffer a constant
+    constexpr int UN = std::max({PF, PF3, PF5}) * W;
     const int n_steps = (zc_end - zc_begin + 1 + UN - 1) / UN * UN;
+    bool blk_full = false;  // the held counts are those of the full z-window
     for (int i0 = zc_begin; i0 < zc_begin + n_steps; i0 += UN) {
+        // The z count of every P3 slice (i0 .. i0+UN-1) and P5 output slice (i0-1-R .. i0+UN-2-R)
+        // of this block is 2R + 1 when they all lie in [R, nz - R): the held counts then change
+        // at most once, on entering the block; any other block refreshes them every step. A
+        // wave-uniform branch around LDS reads and VALU only, no global access inside.
+        const bool was_full = blk_full;
+        blk_full = i0 - 1 - R >= R && i0 + UN - 1 < nz - R;
         static_for<0, UN>([&](auto kc) {
             constexpr int k = decltype(kc)::value;
             const int i = i0 + k;
             const int tid = threadIdx.x;
+            if constexpr (CNTREG) {
+                if (k == 0 ? !(blk_full && was_full) : !blk_full) refresh_counts(i, i - 1 - R);
+            }
             const rsrc_t r_b = rs_in(ob, zb);
             ro5 = make_rsrc(out_base + os, (unsigned)(zs - zo_begin) < nzo ? oslice_bytes : 0u);
             // Fair progress across the waves of a SIMD: the hardware issues oldest-first, which
@@ -1112,17 +1227,20 @@ __global__ __launch_bounds__(NT) void gf3d_fused_kernel(GFParams p) {
             //  phases', ahead of P3 measured +1-4 %, profiles/r05_c0_hoist.txt)
             SA vin3[C::K3 + 2 * R];
             p3_load(tid, vin3);
-            do_p3(tid, i, vin3);
+            do_p3(tid, i, std::integral_constant<int, k % PF3>{}, vin3);
             if constexpr (GF_PRIO) __builtin_amdgcn_s_setprio(1);
             f2 vin5[K5 + 2 * R];
             p5_load(tid, vin5);
-            do_p5(tid, i - 1, std::integral_constant<int, (k + W - 1) % W>{}, vin5);
+            do_p5(tid, i - 1, std::integral_constant<int, (k + W - 1) % W>{},
+                  std::integral_constant<int, k % PF5>{}, vin5);
             lds_barrier();
             if constexpr (GF_PRIO) __builtin_amdgcn_s_setprio(3);
-            // C1: the loads of the next step, P12(i+1), P4(i). Every wait here is for a load
-            // issued a step ago.
-            load_p3v(rs_in(ob + (int64_t)R * sstride, zb + R));  // P3 slice i+1
-            load_p5v(rs_in(ob - sstride, zb - 1));                // P5 slice i-R
+            // C1: the loads of the next steps, P12(i+1), P4(i). Every wait here is for a load
+            // issued a step ago or earlier.
+            load_p3v(std::integral_constant<int, k % PF3>{},  // P3 slice i+PF3
+                     rs_in(ob + (int64_t)(R + PF3 - 1) * sstride, zb + R + PF3 - 1));
+            load_p5v(std::integral_constant<int, k % PF5>{},  // P5 slice i-R+PF5-1
+                     rs_in(ob + (int64_t)(PF5 - 2) * sstride, zb + PF5 - 2));
             if constexpr (C::ORDER & 2) do_p4(tid);
             using BK = std::integral_constant<int, k % PF>;
             do_p12(tid, std::integral_constant<int, k % W>{}, BK{});
