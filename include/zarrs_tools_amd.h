@@ -388,6 +388,40 @@ int zt_arithmetic_memory_per_chunk(int op, int dtype_a, int dtype_b, int dtype_o
 int zt_arithmetic_apply(zt_ctx* ctx, int op, int dtype_a, const void* a, int dtype_b,
                         const void* b, int64_t n, int dtype_out, void* out);
 
+/* ---- connected-component labelling (an extension: the reference has no such filter) ---------- */
+
+/* labels[i] = 0 where in[i] is background, else the number 1 .. K of i's component. An element is
+ * foreground when its value is not zero: any bit set for bool and the integers (all 64 bits of
+ * the 8-byte types), value != 0 for the four float types (+-0.0 are background; NaNs, subnormals
+ * and infinities are foreground). Two foreground elements are neighbours when their coordinates
+ * differ by at most 1 on every axis and on at most `connectivity` axes (1 = faces, ndim = the
+ * full 3^ndim - 1 neighbourhood; nothing wraps at the array edges); a component is a class of the
+ * transitive closure, and components are numbered in the C order of their first elements, as
+ * scipy.ndimage.label numbers them. Semantics and kernels: DESIGN.md §3.13. */
+/* The tile of the three innermost axes that one workgroup labels in LDS. */
+#define ZT_CC_TILE_Z 8
+#define ZT_CC_TILE_Y 8
+#define ZT_CC_TILE_X 64
+/* An extension. All 13 types in; the eight integer types out (bool and the float types are
+ * ZT_ERR_UNSUPPORTED_DATA_TYPE). */
+int zt_connected_components_is_compatible(int dtype_in, int dtype_out);
+/* An extension. Device bytes of one call: input + scratch + output. Scratch is two index arrays,
+ * 2 * n * 4 bytes (2 * n * 8 when n >= 2^32 - 1 or ZT_CC_INDEX64=1), and a tail of
+ * 64 + 16 * (3^ndim - 1) / 2 bytes (K and the offset table). 0 for an array with a zero extent. */
+int zt_connected_components_memory(int dtype_in, int dtype_out, const int64_t* shape, int ndim,
+                                   uint64_t* bytes);
+/* An extension. Labels the whole C-order device array `in` (shape[ndim], element alignment) into
+ * `out` (same shape, dtype_out, element alignment, not overlapping `in`) on the context's stream
+ * and returns K in *count (may be NULL). connectivity outside [1, ndim] is
+ * ZT_ERR_INVALID_PARAMETERS. When K exceeds dtype_out's maximum the call fails with
+ * ZT_ERR_INVALID_PARAMETERS (`connected_components: K components do not fit TYPE`) and `out` is
+ * not written: labels never wrap. The call synchronises the stream once, to read K before it
+ * writes. A refused scratch allocation is ZT_ERR_OUT_OF_MEMORY. A zero extent is a no-op with
+ * K = 0. There is no per-chunk form: a component may span every chunk. */
+int zt_connected_components_apply_array(zt_ctx* ctx, int dtype_in, const void* in, int dtype_out,
+                                        void* out, const int64_t* shape, int ndim,
+                                        int connectivity, uint64_t* count);
+
 /* ---- zarrs_info reductions (src/info/range.rs, src/info/histogram.rs) ------------------------ */
 
 /* The 12 numeric types; ZT_BOOL is ZT_ERR_UNSUPPORTED_DATA_TYPE (the reference reaches

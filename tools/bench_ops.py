@@ -25,6 +25,11 @@ bytes.
 `--only arithmetic`: the two-array arithmetic filter (arithmetic.hip) on 1024^3: float32 - float32
 -> float32, uint16 + uint16 -> uint16 and float32 * uint8 -> float32, alternated with Rescale on
 float32 -> float32 (the per-byte yardstick).
+`--only connected_components`: the labelling (connected.hip) of 1024^3 uint8 -> uint32 at
+connectivity 1 and 3 on sparse noise, dense noise and a thresholded synth_u16 volume, alternated
+with the Reencode uint8 -> uint32 cast of the same volume (the streaming floor); with scipy
+installed, scipy.ndimage.label on the host as the CPU baseline (`--no-scipy` skips it);
+`--cc-once` calls every labelling once and nothing else, for a kernel trace.
 
 Algorithmic bytes: pyramid = level 0 read once + every level written once (2 B per u16
 element; the fused launches never read an intermediate level back); Gaussian = 4 B read + 4 B written per voxel (the separable passes' intermediates are
@@ -800,6 +805,105 @@ def bench_arithmetic(n, rounds=5, window_s=0.5):
     return res
 
 
+def bench_connected_components(n, rounds=5, window_s=0.5, scipy_baseline=True, once=False):
+    """Connected-component labelling on n^3 uint8 device arrays -> uint32 (connected.hip) at
+    connectivity 1 and 3, on sparse noise (density 0.05), dense noise (0.6: one giant component at
+    connectivity 1) and a thresholded synth_u16 volume (blobs), through ConnectedComponents.apply,
+    alternated in one run with the Reencode uint8 -> uint32 cast of the same volume (one byte read
+    and four written per element: the streaming floor, the yardstick). Windows of at least
+    window_s after a warm-up, `rounds` of each, medians. Every call synchronises the stream once
+    (the host reads K before the labels are written); that wait is inside the windows. With scipy
+    installed, scipy.ndimage.label on the host labels the same volumes (the CPU baseline) and its
+    labels and K are compared with the device's. once=True: every labelling called once, in the
+    order volume by volume, connectivity 1 then 3, and nothing else (for a kernel trace)."""
+    import math
+    import numpy as np
+    import torch
+    import zarrs_tools_amd as zt
+    ctx = zt.default_context(0)
+    stream = torch.cuda.current_stream()
+    shape, total = (n, n, n), n ** 3
+    gen = torch.Generator(device="cuda").manual_seed(2025)
+    noise = torch.rand(shape, device="cuda", generator=gen)
+    u16 = zt.synth_u16(shape)
+    sample = u16.reshape(-1)[:: max(1, total // (1 << 20))].to(torch.float32)
+    level = float(torch.quantile(sample, 0.7))
+    volumes = {"sparse_0.05": (noise < 0.05).to(torch.uint8),
+               "dense_0.6": (noise < 0.6).to(torch.uint8),
+               "blobs": (u16.to(torch.float32) > level).to(torch.uint8)}
+    del noise, u16, sample
+    out = torch.empty(shape, dtype=torch.uint32, device="cuda")
+    cast = zt.PointwiseProgram([zt.Reencode()], "uint8", ["uint32"], shape)
+    filters = {1: zt.ConnectedComponents(1), 3: zt.ConnectedComponents(3)}
+    chunk = (32, 32, 32)
+
+    def label(v, c):
+        return filters[c].apply(zt.DeviceArray(v, chunk, "uint8"),
+                                zt.DeviceArray(out, chunk, "uint32"), ctx=ctx)
+
+    if once:
+        return {"op": "connected_components, one call each",
+                "components": {f"{name}_c{c}": label(v, c)
+                               for name, v in volumes.items() for c in (1, 3)}}
+    ops, counts = {}, {}
+    for name, v in volumes.items():
+        ops[f"{name}_cast_u8_u32"] = (lambda v=v: cast.run(v, out, ctx))
+        for c in (1, 3):
+            counts[f"{name}_c{c}"] = label(v, c)
+            ops[f"{name}_c{c}"] = (lambda v=v, c=c: label(v, c))
+    reps = {}
+    for k, fn in ops.items():  # warm-up, then calls per window until it lasts window_s
+        r = 1
+        while True:
+            t = timed(fn, stream, r)
+            if t * r >= window_s * 1e3:
+                break
+            r = math.ceil(window_s * 1e3 / t * 1.05) + 1
+        reps[k] = r
+    ms = {k: [] for k in ops}
+    for _ in range(rounds):
+        for k, fn in ops.items():
+            ms[k].append(timed(fn, stream, reps[k]))
+    res = {"op": "connected_components uint8 -> uint32 (device-resident)",
+           "config": {"shape": [n] * 3, "rounds": rounds, "window_s": window_s},
+           "foreground": {k: round(float(v.to(torch.float32).mean()), 4)
+                          for k, v in volumes.items()},
+           "ops": {}}
+    for k in ops:
+        v = sorted(ms[k])
+        med = v[len(v) // 2]
+        res["ops"][k] = {"ms": round(med, 4), "ms_min": round(v[0], 4), "ms_max": round(v[-1], 4),
+                         "spread": round((v[-1] - v[0]) / med, 4), "calls_per_window": reps[k],
+                         "ns_per_voxel": round(med * 1e6 / total, 5)}
+        if k in counts:
+            res["ops"][k]["components"] = counts[k]
+            y = res["ops"][k.rsplit("_c", 1)[0] + "_cast_u8_u32"]
+            res["ops"][k]["ratio_to_cast"] = round(med / y["ms"], 3)
+        else:
+            gbs = total * 5 / (med / 1e3) / 1e9
+            res["ops"][k].update({"GB/s": round(gbs, 1), "hbm_frac": round(gbs / HBM_PEAK_GBS, 4)})
+    if scipy_baseline:
+        try:
+            from scipy import ndimage
+        except ImportError:
+            ndimage = None
+        if ndimage is not None:
+            for name, v in volumes.items():
+                host = v.cpu().numpy()
+                for c in (1, 3):
+                    t0 = time.perf_counter()
+                    want, k_want = ndimage.label(host, ndimage.generate_binary_structure(3, c))
+                    dt = time.perf_counter() - t0
+                    label(v, c)
+                    got = out.cpu().numpy()
+                    o = res["ops"][f"{name}_c{c}"]
+                    o["scipy_s"] = round(dt, 3)
+                    o["scipy_over_gpu"] = round(dt * 1e3 / o["ms"], 1)
+                    o["equals_scipy"] = bool(k_want == counts[f"{name}_c{c}"] and
+                                             np.array_equal(got, want.astype(np.uint32)))
+    return res
+
+
 def bench_guided4d(shape, chunk, radius, reps):
     """Config T per GPU: a (T, Z, Y, X) f32 time-series share, chunks
     (4, 256, 256, 256), eps 2500. 4-D arrays take the separable per-axis path."""
@@ -906,6 +1010,11 @@ def main():
     ap.add_argument("--t-groups", type=int, nargs=2, default=None,
                     help="config T share: (t groups, z groups) of the 8-GPU split")
     ap.add_argument("--t-rank", type=int, default=None)
+    ap.add_argument("--no-scipy", action="store_true",
+                    help="connected_components: skip the scipy.ndimage.label baseline")
+    ap.add_argument("--cc-once", action="store_true",
+                    help="connected_components: call every labelling once, nothing else (for a "
+                         "kernel trace)")
     a = ap.parse_args()
     only = set(a.only.split(","))
     if "tshare" in only:
@@ -948,6 +1057,9 @@ def main():
         print(json.dumps(bench_compare(a.gaussian_size)), flush=True)
     if "arithmetic" in only:  # with the float32 rescale yardstick, alternated
         print(json.dumps(bench_arithmetic(a.gaussian_size)), flush=True)
+    if "connected_components" in only:  # with the reencode uint8 -> uint32 yardstick, alternated
+        print(json.dumps(bench_connected_components(
+            a.gaussian_size, scipy_baseline=not a.no_scipy, once=a.cc_once)), flush=True)
 
 
 if __name__ == "__main__":

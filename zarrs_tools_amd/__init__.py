@@ -17,6 +17,7 @@ from .filter import (  # noqa: E402
     Clamp,
     chunk_occupancy,
     Compare,
+    ConnectedComponents,
     Context,
     Crop,
     DeviceArray,
@@ -63,4 +64,5 @@ __all__ = [
     "chunk_occupancy",
     "RankFilter", "Median", "Minimum", "Maximum",
     "Arithmetic", "ARITHMETIC_OPERATORS",
+    "ConnectedComponents",
 ]

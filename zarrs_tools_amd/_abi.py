@@ -80,6 +80,15 @@ PW_MAX_OPS = 8
 AR_OPERATORS = {"add": 0, "subtract": 1, "multiply": 2, "divide": 3, "minimum": 4, "maximum": 5,
                 "absolute_difference": 6}
 
+# ZT_CC_TILE_Z / Y / X: the tile of the three innermost axes that one workgroup of the
+# connected-component labelling owns; the scratch tail of a call (zt_connected_components_memory)
+CC_TILE = (8, 8, 64)
+
+
+def cc_tail_bytes(ndim: int) -> int:
+    """The fixed part of the labelling's scratch: K and the offset table of a rank-ndim array."""
+    return 64 + 16 * ((3 ** int(ndim) - 1) // 2)
+
 
 class PointwiseOp(ctypes.Structure):
     """zt_pointwise_op (include/zarrs_tools_amd.h)."""
@@ -229,6 +238,10 @@ def lib() -> ctypes.CDLL:
         "zt_store_arithmetic": ([ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, c_int,
                                  ctypes.c_char_p, c_int, c_int, ctypes.c_int64, ctypes.c_int64,
                                  c_int, c_int, ctypes.POINTER(StoreStats)], c_int),
+        "zt_connected_components_is_compatible": ([c_int, c_int], c_int),
+        "zt_connected_components_memory": ([c_int, c_int, i64p, c_int, u64p], c_int),
+        "zt_connected_components_apply_array": ([vp, c_int, vp, c_int, vp, i64p, c_int, c_int,
+                                                 u64p], c_int),
         "zt_range_is_compatible": ([c_int], c_int),
         "zt_histogram_is_compatible": ([c_int], c_int),
         "zt_range_init": ([vp, vp], c_int),

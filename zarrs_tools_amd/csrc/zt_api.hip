@@ -1562,6 +1562,108 @@ int zt_arithmetic_apply(zt_ctx* ctx, int op, int dtype_a, const void* a, int dty
     return ZT_OK;
 }
 
+// ---- connected-component labelling (an extension; connected.hip) --------------------------------
+
+static_assert(ZT_CC_TILE_Z == zt::kCcTileZ && ZT_CC_TILE_Y == zt::kCcTileY &&
+                  ZT_CC_TILE_X == zt::kCcTileX,
+              "the public header and the kernels agree on the tile");
+
+namespace {
+
+// the largest label an integer output type holds; 0 for bool and the float types
+uint64_t cc_label_max(int dtype) {
+    switch (dtype) {
+    case ZT_INT8: return 0x7Full;
+    case ZT_INT16: return 0x7FFFull;
+    case ZT_INT32: return 0x7FFFFFFFull;
+    case ZT_INT64: return 0x7FFFFFFFFFFFFFFFull;
+    case ZT_UINT8: return 0xFFull;
+    case ZT_UINT16: return 0xFFFFull;
+    case ZT_UINT32: return 0xFFFFFFFFull;
+    case ZT_UINT64: return ~0ull;
+    default: return 0;
+    }
+}
+
+}  // namespace
+
+int zt_connected_components_is_compatible(int dtype_in, int dtype_out) {
+    for (int d : {dtype_in, dtype_out})
+        if (!valid_dtype(d))
+            return fail(ZT_ERR_UNSUPPORTED_DATA_TYPE, "Unsupported data type code %d", d);
+    if (cc_label_max(dtype_out) == 0)
+        return fail(ZT_ERR_UNSUPPORTED_DATA_TYPE,
+                    "connected_components: labels need an integer output type, not %s",
+                    dtype_name(dtype_out));
+    return ZT_OK;
+}
+
+int zt_connected_components_memory(int dtype_in, int dtype_out, const int64_t* shape, int ndim,
+                                   uint64_t* bytes) {
+    if (int rc = zt_connected_components_is_compatible(dtype_in, dtype_out)) return rc;
+    if (int rc = check_shape(shape, ndim, "shape")) return rc;
+    if (!bytes) return fail(ZT_ERR_INVALID_PARAMETERS, "null pointer");
+    const int64_t n = numel(shape, ndim);
+    *bytes = n == 0 ? 0
+                    : (uint64_t)n * (zt::dtype_size(dtype_in) + zt::dtype_size(dtype_out)) +
+                          zt::cc_scratch_bytes(n, zt::cc_index64(n), ndim);
+    return ZT_OK;
+}
+
+int zt_connected_components_apply_array(zt_ctx* ctx, int dtype_in, const void* in, int dtype_out,
+                                        void* out, const int64_t* shape, int ndim,
+                                        int connectivity, uint64_t* count) {
+    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = zt_connected_components_is_compatible(dtype_in, dtype_out)) return rc;
+    if (int rc = check_shape(shape, ndim, "shape")) return rc;
+    if (connectivity < 1 || connectivity > ndim)
+        return fail(ZT_ERR_INVALID_PARAMETERS,
+                    "connected_components: connectivity %d not in [1, %d]", connectivity, ndim);
+    if (count) *count = 0;
+    const int64_t n = numel(shape, ndim);
+    if (n == 0) return ZT_OK;
+    if (n > zt::kCcMaxElems)
+        return fail(ZT_ERR_INVALID_PARAMETERS,
+                    "connected_components: %lld elements are more than %lld", (long long)n,
+                    (long long)zt::kCcMaxElems);
+    int64_t tiles = 1;
+    for (int d = 0; d < ndim; ++d) {
+        const int t = d == ndim - 1 ? ZT_CC_TILE_X : d == ndim - 2 ? ZT_CC_TILE_Y
+                      : d == ndim - 3 ? ZT_CC_TILE_Z : 1;
+        tiles *= (shape[d] + t - 1) / t;
+    }
+    if (tiles > 0x7FFFFFFFll)
+        return fail(ZT_ERR_INVALID_PARAMETERS,
+                    "connected_components: %lld tiles are more than one launch holds",
+                    (long long)tiles);
+    if (!in || !out) return fail(ZT_ERR_INVALID_PARAMETERS, "null data pointer");
+    if (in == out) return fail(ZT_ERR_INVALID_PARAMETERS, "input and output must differ");
+    if (((uintptr_t)in % zt::dtype_size(dtype_in)) != 0 ||
+        ((uintptr_t)out % zt::dtype_size(dtype_out)) != 0)
+        return fail(ZT_ERR_INVALID_PARAMETERS, "data pointers must be element aligned");
+    DeviceGuard guard(ctx->device);
+    const bool idx64 = zt::cc_index64(n);
+    if (int rc = ctx->ensure_scratch((size_t)zt::cc_scratch_bytes(n, idx64, ndim))) return rc;
+    if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev0, ctx->cur));
+    hipError_t e = zt::launch_cc_label(in, dtype_in, shape, ndim, connectivity, idx64,
+                                       ctx->scratch, ctx->cur);
+    if (e != hipSuccess) return hip_fail(e, "connected components launch");
+    // K comes back before anything is written: labels never wrap
+    uint64_t k = 0;
+    ZT_HIP(hipMemcpyAsync(&k, zt::cc_count_ptr(ctx->scratch, n, idx64), sizeof(k),
+                          hipMemcpyDeviceToHost, ctx->cur));
+    ZT_HIP(hipStreamSynchronize(ctx->cur));
+    if (k > cc_label_max(dtype_out))
+        return fail(ZT_ERR_INVALID_PARAMETERS,
+                    "connected_components: %llu components do not fit %s", (unsigned long long)k,
+                    dtype_name(dtype_out));
+    e = zt::launch_cc_write(ctx->scratch, n, idx64, out, dtype_out, ctx->cur);
+    if (e != hipSuccess) return hip_fail(e, "connected components write launch");
+    if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev1, ctx->cur));
+    if (count) *count = k;
+    return ZT_OK;
+}
+
 // ---- zarrs_info reductions (range.rs, histogram.rs) --------------------------------------------
 
 namespace {

@@ -251,6 +251,32 @@ int arithmetic_max_blocks();
 hipError_t launch_arithmetic(const void* a, int dt_a, const void* b, int dt_b, void* out,
                              int dt_out, int64_t n, int op, hipStream_t s);
 
+// Connected-component labelling (connected.hip; an extension, no reference filter; DESIGN.md
+// §3.13) of a contiguous C-order array of `shape` at element alignment. A workgroup of the local
+// phase owns a tile of kCcTileZ x kCcTileY x kCcTileX elements of the three innermost axes
+// (ZT_CC_TILE_* in the public header). Scratch (cc_scratch_bytes) holds two arrays of n indices
+// (uint32_t, or uint64_t when cc_index64(n): n >= 2^32 - 1, or ZT_CC_INDEX64=1) and a tail: the
+// component count K (kCcTailHeader bytes) and the host-built table of backward offsets, sized for
+// the full neighbourhood of the rank. launch_cc_label runs everything up to the numbering and
+// leaves K at cc_count_ptr; launch_cc_write then stores out[i] = label of i's component, or 0.
+constexpr int kCcTileZ = 8, kCcTileY = 8, kCcTileX = 64;
+constexpr int kCcBlockElems = 4096;  // elements of a numbering block
+constexpr int kCcTailHeader = 64;
+constexpr int64_t kCcMaxElems = (int64_t)1 << 38;
+struct CcOffset {
+    int64_t delta;  // linear index of the neighbour minus that of the element
+    uint32_t d;     // offset + 1 on axis k of the shape padded in front to kMaxDims, 2 bits each
+    uint32_t reserved;
+};
+bool cc_index64(int64_t n);
+uint64_t cc_tail_bytes(int ndim);
+uint64_t cc_scratch_bytes(int64_t n, bool idx64, int ndim);
+const uint64_t* cc_count_ptr(const void* scratch, int64_t n, bool idx64);
+hipError_t launch_cc_label(const void* in, int dtype_in, const int64_t* shape, int ndim,
+                           int connectivity, bool idx64, void* scratch, hipStream_t s);
+hipError_t launch_cc_write(const void* scratch, int64_t n, bool idx64, void* out, int dtype_out,
+                           hipStream_t s);
+
 // zarrs_info reductions (info.hip; src/info/range.rs, src/info/histogram.rs) over a contiguous
 // run of n elements of `dtype` (the 12 numeric types) at element alignment.
 // Range: `state` is two device u64 words (smallest key, largest key) that accumulate across

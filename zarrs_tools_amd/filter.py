@@ -23,6 +23,8 @@ Names, argument meaning and error behaviour follow LDeakin/zarrs_tools 0.7.2:
     ``combine_compares`` joins partial results)
   - ``Arithmetic``: an extension with no counterpart in the reference (two arrays in, one out);
     its semantics are DESIGN.md §3.12
+  - ``ConnectedComponents``: an extension with no counterpart in the reference (labels of the
+    connected sets of non-zero elements); its semantics are DESIGN.md §3.13
   - ``chunk_occupancy`` <- zarrs' ``store_empty_chunks = false`` (which chunks of a device
     array hold anything but the fill value)
   - ``ArraySubsetOverlap`` <- src/filter/array_subset_overlap.rs:4-52
@@ -1307,6 +1309,81 @@ class Arithmetic:
         x, dtype_a = _info_run(first)
         y, dtype_b = _info_run(second)
         self._run(x, dtype_a, y, dtype_b, output.data, output.dtype, ctx)
+
+
+CC_DEFAULT_DATA_TYPE = "uint32"
+
+
+class ConnectedComponents:
+    """An extension with no counterpart in the reference: every connected set of
+    non-zero elements gets its own integer 1 .. K, background 0, components numbered in the C
+    order of their first elements (scipy.ndimage.label's numbering). Two foreground elements are
+    neighbours when their coordinates differ by at most 1 on every axis and on at most
+    `connectivity` axes: 1 = faces (the default), the array's rank = the full neighbourhood. All
+    13 types in; the eight integer types out, uint32 by default. Labelling is a whole-array
+    operation (a component may span every chunk), so there is no per-chunk form."""
+
+    def __init__(self, connectivity: int = 1):
+        self.connectivity = int(connectivity)
+        if self.connectivity < 1:
+            raise _invalid(f"connected_components: connectivity {self.connectivity} not in "
+                           "[1, rank]")
+
+    def name(self) -> str:
+        return "connected components"
+
+    def check_connectivity(self, ndim: int) -> None:
+        """InvalidParameters unless 1 <= connectivity <= ndim."""
+        if not 1 <= self.connectivity <= int(ndim):
+            raise _invalid(f"connected_components: connectivity {self.connectivity} not in "
+                           f"[1, {int(ndim)}]")
+
+    def is_compatible(self, dtype_in: str, dtype_out: str) -> None:
+        check(lib().zt_connected_components_is_compatible(_info_dtype(dtype_in),
+                                                          _info_dtype(dtype_out)))
+
+    def memory(self, dtype_in: str, dtype_out: str, shape) -> int:
+        """Device bytes of one call on an array of `shape`: input + scratch + output."""
+        self.check_connectivity(len(shape))
+        out = ctypes.c_uint64()
+        check(lib().zt_connected_components_memory(
+            _info_dtype(dtype_in), _info_dtype(dtype_out), i64_array(shape), len(shape),
+            ctypes.byref(out)))
+        return int(out.value)
+
+    def _run(self, x, dtype_in, out, dtype_out, ctx) -> int:
+        if tuple(out.shape) != tuple(x.shape):
+            raise _invalid(f"Array shapes do not match: {list(x.shape)} vs {list(out.shape)}")
+        if x.device != out.device:
+            raise _invalid("connected_components: the arrays are on different devices")
+        if not out.is_contiguous():
+            raise _invalid("connected_components: the output must be contiguous")
+        self.is_compatible(dtype_in, dtype_out)
+        self.check_connectivity(x.dim())
+        ctx = ctx or default_context(x.device.index)
+        count = ctypes.c_uint64()
+        check(lib().zt_connected_components_apply_array(
+            ctx.handle, DTYPES[dtype_in], _ptr(x), DTYPES[dtype_out], _ptr(out),
+            i64_array(x.shape), x.dim(), self.connectivity, ctypes.byref(count)))
+        return int(count.value)
+
+    def apply_ndarray(self, v, dtype_out: Optional[str] = None, ctx: Optional[Context] = None,
+                      out=None):
+        """Labels a device tensor; returns (labels, K). labels is a new tensor of `dtype_out`
+        (default uint32), or `out` (contiguous, of `dtype_out`, not overlapping the input). When
+        K does not fit `dtype_out` the call raises InvalidParameters and writes nothing."""
+        x, dtype_in = _info_run(v)
+        dtype_out = dtype_out or (dtype_of(out) if out is not None else CC_DEFAULT_DATA_TYPE)
+        if out is None:
+            self.is_compatible(dtype_in, dtype_out)
+            out = _torch().empty(tuple(x.shape), dtype=torch_dtype(dtype_out), device=x.device)
+        return out, self._run(x, dtype_in, out, dtype_out, ctx)
+
+    def apply(self, input: DeviceArray, output: DeviceArray,
+              ctx: Optional[Context] = None) -> int:
+        """The filter's `apply` over device-resident arrays; returns K."""
+        x, dtype_in = _info_run(input)
+        return self._run(x, dtype_in, output.data, output.dtype, ctx)
 
 
 class Downsample:

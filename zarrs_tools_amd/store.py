@@ -462,6 +462,113 @@ def summed_area_table(input_path, output_path, data_type: Optional[str] = None, 
     return _stats(st)
 
 
+def device_available_bytes(device: int = 0) -> int:
+    """Device memory a store step may budget (as device_available_bytes in host/zt_store.cpp):
+    ZT_STORE_DEVICE_MEMORY if set, else the free memory of `device`."""
+    env = os.environ.get("ZT_STORE_DEVICE_MEMORY")
+    if env:
+        return int(env)
+    import torch
+    return int(torch.cuda.mem_get_info(device)[0])
+
+
+def connected_components_output(data_type: Optional[str] = None, encoding=None):
+    """(output data type, encoding) of a labelling's output array: an explicit data type
+    (`data_type` or the encoding's) wins, else uint32; the fill value is 0 unless given."""
+    enc = dict(encoding) if isinstance(encoding, dict) else (
+        json.loads(encoding) if encoding else {})
+    dt = enc.get("data_type") or data_type or "uint32"
+    enc["data_type"] = dt
+    if enc.get("fill_value") is None:
+        enc["fill_value"] = 0
+    return dt, enc
+
+
+def connected_components(input_path, output_path, connectivity: int = 1,
+                         data_type: Optional[str] = None, device: int = 0, nthreads: int = 0,
+                         encoding=None) -> dict:
+    """zarrs_filter connected-components INPUT OUTPUT [--connectivity C] [--data-type T]: labels
+    the connected sets of non-zero elements (filter.ConnectedComponents; uint32 labels and fill
+    value 0 unless given). A component may span every chunk, so the whole array is read into
+    device memory, labelled there and written once; there is no store -> store path, and an
+    array that does not fit 80 % of the free device memory fails with ZT_ERR_OUT_OF_MEMORY before
+    anything is read. When K does not fit the output type the step fails with InvalidParameters,
+    writes no chunk and publishes no zarr.json. Returns the run stats and "components": K."""
+    import time
+    from . import filter as F
+    from .device_io import _read_pieces, _row_spans, read_to_device, write_from_device
+    t0 = time.perf_counter()
+    info = open_array(input_path)
+    filt = F.ConnectedComponents(connectivity)
+    dt, enc = connected_components_output(data_type, encoding)
+    filt.is_compatible(info.data_type, dt)
+    filt.check_connectivity(info.ndim)
+    for name in ("zarr.json", PENDING_METADATA):  # the output is not finished until the end
+        try:
+            os.remove(os.path.join(output_path, name))
+        except FileNotFoundError:
+            pass
+    # budgets, before anything is read: the array, its labels and the scratch on the device; the
+    # pinned pieces of the read and the pinned rows of the write on the host
+    shape = [int(s) for s in info.shape]
+    in_esz, out_esz = NUMPY[info.data_type]().itemsize, NUMPY[dt]().itemsize
+    need = filt.memory(info.data_type, dt, shape)
+    budget = device_available_bytes(device) // 10 * 8
+    no_fallback = ("connected_components labels the whole array in device memory (a component "
+                   "may span every chunk): there is no store -> store path to fall back to")
+    if need > budget:
+        raise _abi.FilterError(
+            _abi.ERR_OUT_OF_MEMORY,
+            "There is not enough available memory to process the array: it needs "
+            f"{need} bytes of device memory (input, labels and two index arrays) and 80 % of "
+            f"the available memory is {budget}; {no_fallback}")
+    host_need = 0
+    if all(s > 0 for s in shape):
+        pieces = _read_pieces([0] * info.ndim, shape, info.chunk_shape, in_esz)
+        plane2 = int(np.prod(shape[2:])) if info.ndim > 2 else 1
+        piece_b = max((b - a) * (yb - ya) * plane2 for a, b, ya, yb in pieces) * in_esz
+        out_chunk0 = int((enc.get("shard_shape") or enc.get("chunk_shape") or info.chunk_shape)[0])
+        rows = max(b - a for a, b in _row_spans(0, shape[0], out_chunk0))
+        row_b = rows * int(np.prod(shape[1:])) * out_esz
+        host_need = max(min(3, len(pieces)) * piece_b,
+                        min(2, -(-shape[0] // out_chunk0)) * row_b)
+    host_budget = host_available_bytes() // 10 * 8
+    if host_need > host_budget:
+        raise _abi.FilterError(
+            _abi.ERR_OUT_OF_MEMORY,
+            "There is not enough available memory to process the array: its pinned host "
+            f"buffers need {host_need} bytes and 80 % of the available memory is {host_budget}; "
+            f"{no_fallback}")
+    create_output(input_path, output_path, dt, None, enc)
+    hold_metadata(output_path)  # "not finished" until the chunks are written
+    out_info = open_array(output_path)
+    import torch
+    t1 = time.perf_counter()
+    x = read_to_device(input_path, device, nthreads)
+    t_read = time.perf_counter() - t1
+    y = torch.empty(tuple(shape), dtype=F.torch_dtype(dt), device=x.device)
+    ctx = F.default_context(device)
+    t1 = time.perf_counter()
+    try:
+        k = filt.apply(F.DeviceArray(x, info.chunk_shape, info.data_type),
+                       F.DeviceArray(y, out_info.chunk_shape, dt), ctx=ctx)
+        ctx.synchronize()
+    finally:
+        ctx.release_scratch()
+    t_kernel = time.perf_counter() - t1
+    del x
+    t1 = time.perf_counter()
+    elided = write_from_device(output_path, y, nthreads) or 0
+    publish_metadata(output_path)
+    t_write = time.perf_counter() - t1
+    n = int(np.prod(shape)) if shape else 0
+    return {"wall_s": time.perf_counter() - t0, "decode_s": t_read, "encode_s": t_write,
+            "h2d_s": 0.0, "kernel_s": t_kernel, "d2h_s": 0.0, "bytes_read": n * in_esz,
+            "bytes_written": n * out_esz, "voxels": n, "rows": 0, "threads": int(nthreads),
+            "rows_in_flight": 0, "double_buffered": 0, "chunks_elided": int(elided),
+            "device_resident": True, "components": int(k)}
+
+
 def pointwise_output(filt, input_data_type: str, data_type: Optional[str] = None, encoding=None):
     """(output data type, encoding) of a per-element filter's output array, as
     output_array_builder decides it (filter_traits.rs:47-82): an explicit data type (`data_type`

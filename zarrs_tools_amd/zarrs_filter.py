@@ -1,6 +1,7 @@
 """``zarrs_filter`` for the on-path filters (guided_filter, downsample, gaussian,
 summed_area_table, the rank filters median, minimum, maximum, the per-element reencode, crop,
-rescale, clamp, equal, replace_value and the two-array arithmetic) over Zarr V3 stores.
+rescale, clamp, equal, replace_value, the two-array arithmetic and the whole-array
+connected_components) over Zarr V3 stores.
 
 Mirrors src/bin/zarrs_filter.rs (LDeakin/zarrs_tools 0.7.2) for the filters this framework
 accelerates:
@@ -17,7 +18,9 @@ accelerates:
                                         | rescale IN OUT MULTIPLY ADD [--add-first]
                                         | clamp IN OUT MIN MAX | equal IN OUT VALUE
                                         | replace-value IN OUT VALUE REPLACE
-                                        | arithmetic IN OUT OPERATOR OTHER [--data-type T]]
+                                        | arithmetic IN OUT OPERATOR OTHER [--data-type T]
+                                        | connected-components IN OUT [--connectivity C]
+                                              [--data-type T]]
 
 * subcommand arguments as GuidedFilterArguments (guided_filter.rs:25-33),
   DownsampleArguments (downsample.rs:20-33, STRIDE comma delimited) and GaussianArguments
@@ -34,10 +37,17 @@ accelerates:
   OUT = IN OPERATOR OTHER element by element, OPERATOR one of add, subtract, multiply, divide,
   minimum, maximum, absolute-difference (hyphens on the command line, snake_case in a run
   config), OTHER a second array of IN's shape and of any type, chunk grid and codecs;
+  connected-components (an extension: the reference has no labelling) gives
+  every connected set of non-zero elements its own integer 1 .. K in the C order of the sets'
+  first elements, background 0; two elements are neighbours when their coordinates differ by at
+  most 1 on every axis and on at most C axes (--connectivity, default 1: faces); OUT is uint32
+  with fill value 0 unless --data-type names another integer type, and the step fails, writing
+  nothing, when K does not fit it; the step logs K;
 * a JSON run config is a list of {"filter": "guided_filter" | "downsample" | "gaussian" |
   "summed_area_table" | "median" | "minimum" | "maximum" | "reencode" | "crop" | "rescale" |
-  "clamp" | "equal" | "replace_value" | "arithmetic", "input", "output", ...args (kernel_half_size; offset, shape, multiply, add, add_first, min, max, value, replace
-  for the per-element filters; operator, other for arithmetic, whose "other" is a path or the
+  "clamp" | "equal" | "replace_value" | "arithmetic" | "connected_components", "input", "output", ...args (kernel_half_size; offset, shape, multiply, add, add_first, min, max, value, replace
+  for the per-element filters; connectivity for connected_components; operator, other for
+  arithmetic, whose "other" is a path or the
   "$name" of a temporary that an earlier step wrote), "data_type"}, with "$name" meaning a named
   temporary array under --tmp and an omitted input meaning the previous filter's output (zarrs_filter.rs:106-138,
   :338-381);
@@ -51,6 +61,8 @@ accelerates:
   `--no-pointwise-fusion` launches them one by one); an arithmetic step is never part of such
   a chain (it runs store -> store and ends the chain before it), and a temporary that a later
   arithmetic step reads as its "other" is written to the store by the step that produces it;
+  a connected_components step may be part of such a chain (equal -> connected_components labels
+  a mask that never touches the store), and the chain's budget then counts its two index arrays;
 * every filter takes the reencoding arguments (ZarrReencodingArgs, lib.rs:274-377: -d/--data-type,
   -f/--fill-value, --separator, -c/--chunk-shape, -s/--shard-shape, --array-to-array-codecs,
   --array-to-bytes-codec, --bytes-to-bytes-codecs, --dimension-names, --attributes,
@@ -64,7 +76,10 @@ accelerates:
 
 gradient_magnitude is rejected with FilterError::Other: it runs from the library only
 (DESIGN.md §1). A summed-area table's chunk rows each need the previous row's last plane, so with
---gpus > 1 that step runs in one process on the first device (`rows_splittable`); the other
+--gpus > 1 that step runs in one process on the first device (`rows_splittable`); so does
+connected_components, whose unit of work is the whole array: it is read into device memory,
+labelled and written once, and fails with the out-of-memory error when it does not fit (there is
+no store -> store path for it). The other
 filters' rows, the per-element ones included, are split over the processes. `--chunk-limit N`
 bounds the chunks in flight (decoded input rows + output rows being computed or encoded, and the
 host worker threads) at N, down to the pipeline's unit of one slab and one output row
@@ -87,19 +102,22 @@ import numpy as np
 
 from . import _abi
 from . import store as S
+from .device_io import _read_pieces, _row_spans, read_to_device, write_from_device  # noqa: F401
 
 POINTWISE = ("reencode", "crop", "rescale", "clamp", "equal", "replace_value")
 RANK = ("median", "minimum", "maximum")
 BINARY = ("arithmetic",)  # two arrays in: "input" and "other"
+WHOLE_ARRAY = ("connected_components",)  # no chunk rows at all: the array is the unit of work
 ON_PATH = ("guided_filter", "downsample", "gaussian", "summed_area_table") + RANK + POINTWISE + \
-    BINARY
+    BINARY + WHOLE_ARRAY
 
 
 def rows_splittable(name: str) -> bool:
     """Whether a store step's output chunk rows are independent, so that --gpus > 1 may split
     them over processes. A summed-area table's rows are not: each row's axis-0 sum starts from
-    the previous row's last plane (summed_area_table.rs:69, :94-97)."""
-    return name != "summed_area_table"
+    the previous row's last plane (summed_area_table.rs:69, :94-97). Nor are a labelling's: a
+    connected component may span every chunk."""
+    return name != "summed_area_table" and name not in WHOLE_ARRAY
 
 
 def _parse_stride(s: str):
@@ -266,6 +284,14 @@ def build_parser() -> argparse.ArgumentParser:
     ar.add_argument("operator", choices=[o.replace("_", "-") for o in _abi.AR_OPERATORS])
     ar.add_argument("other")
     _add_reencode_args(ar)
+    cc = sub.add_parser("connected-components",
+                        help="Label the connected sets of non-zero elements.")
+    cc.add_argument("input")
+    cc.add_argument("output")
+    cc.add_argument("--connectivity", type=int, default=1,
+                    help="neighbours differ on at most this many axes (1: faces, the default; "
+                         "the rank: the full neighbourhood)")
+    _add_reencode_args(cc)
     return ap
 
 
@@ -302,6 +328,10 @@ def _steps_from_cli(a) -> list:
                  "operator": a.operator.replace("-", "_"), "other": a.other,
                  "data_type": a.data_type, "chunk_limit": a.filter_chunk_limit,
                  **_reencode_of(a)}]
+    if a.filter == "connected-components":
+        return [{"filter": "connected_components", "input": a.input, "output": a.output,
+                 "connectivity": a.connectivity, "data_type": a.data_type,
+                 "chunk_limit": a.filter_chunk_limit, **_reencode_of(a)}]
     return []
 
 
@@ -396,7 +426,20 @@ def step_encoding(step: dict, in_data_type: str):
     if step.get("filter") in POINTWISE:
         _dt, enc = S.pointwise_output(pointwise_filter(step), in_data_type,
                                       step.get("data_type"), enc)
+    if step.get("filter") in WHOLE_ARRAY:  # labels: uint32, fill value 0
+        _dt, enc = S.connected_components_output(step.get("data_type"), enc)
     return enc
+
+
+def connectivity_of(step: dict) -> int:
+    """The connectivity of a connected_components run-config step (default 1: faces)."""
+    c = step.get("connectivity")
+    try:
+        return 1 if c is None else int(c)
+    except (TypeError, ValueError):
+        raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS,
+                                     f"connected_components: connectivity {c!r} is not an "
+                                     "integer") from None
 
 
 def _step_params(step, info):
@@ -410,6 +453,12 @@ def _step_params(step, info):
         f.is_compatible(info.data_type, dt)
         f.op(info.data_type, dt)  # value / replace must fit the types
         return f, f.output_shape(info.shape), dt
+    if name == "connected_components":
+        f = F.ConnectedComponents(connectivity_of(step))
+        dt, _enc = S.connected_components_output(step.get("data_type"), encoding_of(step))
+        f.is_compatible(info.data_type, dt)
+        f.check_connectivity(info.ndim)
+        return f, tuple(info.shape), dt
     dt = step.get("data_type") or (encoding_of(step) or {}).get("data_type") or info.data_type
     if name == "guided_filter":
         if "epsilon" not in step or "radius" not in step:
@@ -467,164 +516,6 @@ def allocation_refused(e: BaseException) -> bool:
                                             "hiphostmalloc" in msg or "cudahostalloc" in msg)
 
 
-def _row_spans(start0: int, n0: int, chunk0: int) -> list:
-    """[a, b) pieces of the axis-0 range [start0, start0 + n0) cut at the chunk grid, so that
-    every chunk (or shard) is decoded / encoded by one piece only."""
-    spans, a, end = [], start0, start0 + n0
-    while a < end:
-        b = min((a // chunk0 + 1) * chunk0, end)
-        spans.append((a, b))
-        a = b
-    return spans
-
-
-def _read_pieces(start, shape, chunk_shape, esz: int) -> list:
-    """The pieces a box read is pipelined in: chunk rows of axis 0, cut along axis 1 at the chunk
-    grid into pieces of about ZT_READ_PIECE_KB (default 512 MiB; 0: whole rows). Each chunk is
-    still decoded once, but a pinned buffer holds a piece instead of a whole chunk row: pinning
-    three 2 GB rows per process made 2048^3 u16 box reads 2x slower
-    (profiles/r04_octant_workers*.json). [(a, b, ya, yb)]; ya, yb = 0, 1 for 1-D arrays."""
-    nd = len(shape)
-    spans = _row_spans(start[0], shape[0], int(chunk_shape[0])) if shape[0] > 0 else []
-    if nd < 2:
-        return [(a, b, 0, 1) for a, b in spans]
-    target = int(os.environ.get("ZT_READ_PIECE_KB", "524288")) << 10
-    plane2 = int(np.prod(shape[2:])) if nd > 2 else 1
-    cy = int(chunk_shape[1])
-    out = []
-    for a, b in spans:
-        if target > 0:
-            m = max(1, target // max(1, (b - a) * cy * plane2 * esz))
-            out += [(a, b, ya, yb) for ya, yb in _row_spans(start[1], shape[1], cy * m)]
-        else:
-            out.append((a, b, start[1], start[1] + shape[1]))
-    return out
-
-
-def read_to_device(path, device: int, nthreads: int = 0, start=None, shape=None):
-    """The box [start, start + shape) of a store array (the whole array by default) decoded into
-    HBM, overlapped chunk row by chunk row: a host thread decodes row k+1
-    into one of three pinned row buffers while row k is copied host-to-device on a side stream
-    (the reference copies level 0 then streams it chunk by chunk, zarrs_ome.rs:341-366,
-    631-714). Each chunk is decoded once. bfloat16 arrays come back as torch.bfloat16."""
-    import torch
-    from concurrent.futures import ThreadPoolExecutor
-    from . import filter as F
-    info = S.open_array(path)
-    nd = info.ndim
-    start = [0] * nd if start is None else [int(v) for v in start]
-    shape = list(info.shape) if shape is None else [int(v) for v in shape]
-    store_dt = "uint16" if info.data_type == "bfloat16" else info.data_type
-    tdt = F.torch_dtype(store_dt)
-    dev = torch.device("cuda", device)
-    x = torch.empty(tuple(shape), dtype=tdt, device=dev)
-    if all(v > 0 for v in shape):
-        pieces = _read_pieces(start, shape, info.chunk_shape, x.element_size())
-
-        def pshape(p):
-            a, b, ya, yb = p
-            return [b - a, yb - ya] + shape[2:] if nd >= 2 else [b - a]
-
-        n_max = max(int(np.prod(pshape(p))) for p in pieces)
-        nbuf = min(3, len(pieces))
-        bufs = [torch.empty((n_max,), dtype=tdt, pin_memory=True) for _ in range(nbuf)]
-        evs = [None] * nbuf
-        stream = torch.cuda.Stream(device=dev)
-        # x was allocated on the caller's current stream: order the copies after any work that
-        # stream still has queued on the block the caching allocator handed back
-        stream.wait_stream(torch.cuda.current_stream(dev))
-
-        def decode(k):
-            a, b, ya, yb = pieces[k]
-            ps = pshape(pieces[k])
-            h = bufs[k % nbuf][:int(np.prod(ps))].view(ps)
-            S.read_array(path, [a, ya] + start[2:] if nd >= 2 else [a], ps, nthreads=nthreads,
-                         out=h.numpy())
-            return h
-
-        with ThreadPoolExecutor(1) as ex:
-            fut = ex.submit(decode, 0)
-            for k, (a, b, ya, yb) in enumerate(pieces):
-                h = fut.result()
-                if k + 1 < len(pieces):
-                    ev = evs[(k + 1) % nbuf]
-                    if ev is not None:
-                        ev.synchronize()  # the H2D that last read this buffer has finished
-                    fut = ex.submit(decode, k + 1)
-                with torch.cuda.stream(stream):
-                    if nd >= 2:
-                        x[a - start[0]:b - start[0], ya - start[1]:yb - start[1]].copy_(
-                            h, non_blocking=True)
-                    else:
-                        x[a - start[0]:b - start[0]].copy_(h, non_blocking=True)
-                    ev = torch.cuda.Event()
-                    ev.record(stream)
-                evs[k % nbuf] = ev
-        stream.synchronize()
-    return x.view(torch.bfloat16) if info.data_type == "bfloat16" else x
-
-
-def write_from_device(path, x, nthreads: int = 0, start=None) -> int:
-    """A device tensor (the box at `start`, default the whole array at `path`) into the store,
-    overlapped chunk row by chunk row: row k+1 is copied device-to-host into one of two pinned
-    buffers while a host thread encodes row k. When the calling thread elides empty chunks
-    (store.set_store_empty_chunks(False)) the row's inner chunks are tested on the device first
-    (filter.chunk_occupancy): a row of nothing but the fill value is not copied, and the encoder
-    gets the map. Returns the number of chunks elided."""
-    import torch
-    from concurrent.futures import ThreadPoolExecutor
-    if x.dtype == torch.bfloat16:
-        x = x.view(torch.uint16)
-    info = S.open_array(path)
-    nd = x.dim()
-    start = [0] * nd if start is None else [int(v) for v in start]
-    shape = list(x.shape)
-    if not shape or any(v == 0 for v in shape):
-        return
-    spans = _row_spans(start[0], shape[0], int(info.chunk_shape[0]))
-    plane = int(np.prod(shape[1:])) if nd > 1 else 1
-    rows = max(b - a for a, b in spans)
-    nbuf = min(2, len(spans))
-    bufs = [torch.empty((rows * plane,), dtype=x.dtype, pin_memory=True) for _ in range(nbuf)]
-    futs = [None] * nbuf
-    store_all = S.store_empty_chunks()
-    fill = None
-    if not store_all:  # the fill value's bits, as the tensor's type (bfloat16 travels as uint16)
-        from . import filter as F
-        fill = hex(F.fill_value_bits(S.fill_value_of(path), info.data_type))
-    elided = 0
-
-    def write(h, origin, occ):  # on the encoder thread, with the caller's setting
-        S.set_store_empty_chunks(store_all)
-        S.write_array(path, h, origin, nthreads, occupied=occ)
-        return S.last_elided()[0]
-
-    def skip(origin, row_shape):  # a row of fill: no copy; its files, if any, are removed
-        S.set_store_empty_chunks(store_all)
-        S.write_empty(path, origin, row_shape, nthreads)
-        return S.last_elided()[0]
-
-    with ThreadPoolExecutor(1) as ex:
-        for k, (a, b) in enumerate(spans):
-            if futs[k % nbuf] is not None:
-                elided += futs[k % nbuf].result()  # this buffer's previous row is encoded
-                futs[k % nbuf] = None
-            row = x[a - start[0]:b - start[0]]
-            occ = None
-            if not store_all:
-                occ = F.chunk_occupancy(row, info.inner_chunk_shape, fill).cpu().numpy()
-                if not occ.any():
-                    futs[k % nbuf] = ex.submit(skip, [a] + start[1:], [b - a] + shape[1:])
-                    continue
-            h = bufs[k % nbuf][:(b - a) * plane].view([b - a] + shape[1:])
-            h.copy_(row)
-            futs[k % nbuf] = ex.submit(write, h.numpy(), [a] + start[1:], occ)
-        for f in futs:
-            if f is not None:
-                elided += f.result()
-    return elided
-
-
 def plan_pointwise_fusion(names: list, fuse: bool = True, max_ops: int = 8) -> list:
     """The launches of a device-resident chain: [(i, j)] covering every step in order, (i, j)
     with j > i a maximal run of consecutive per-element steps (at most `max_ops`, a longer run is
@@ -665,8 +556,12 @@ def run_device_chain(steps: list, paths: list, device: int = 0, nthreads: int = 
     # only the arrays that are materialised count: each launch's input and output
     peak = max(_nbytes(plan[i][1].shape, plan[i][1].data_type) + _nbytes(plan[j][2], plan[j][3])
                for i, j in groups)
+    # a labelling's scratch (two index arrays) is larger than its input + output: count it
+    whole = max([plan[k][0].memory(plan[k][1].data_type, plan[k][3], plan[k][2])
+                 for k, st in enumerate(steps) if st.get("filter") in WHOLE_ARRAY], default=0)
     free, _total = torch.cuda.mem_get_info(device)
-    if 2 * peak > budget_frac * free:  # in + out of a step, plus filter scratch of the same order
+    # in + out of a step, plus filter scratch of the same order
+    if max(2 * peak, whole) > budget_frac * free:
         return None
     # the chain input and the last output each pass through one pinned host buffer
     src0 = S.open_array(paths[0])
@@ -699,17 +594,24 @@ def run_device_chain(steps: list, paths: list, device: int = 0, nthreads: int = 
         y = torch.empty(tuple(out_info.shape), dtype=F.torch_dtype(out_info.data_type), device=dev)
         names = "+".join(str(steps[k].get("filter")) for k in range(i, j + 1))
         t1 = time.perf_counter()
+        ret = None
         if j > i:
             prog = F.PointwiseProgram([plan[k][0] for k in range(i, j + 1)], x_dt,
                                       [plan[k][3] for k in range(i, j + 1)], x.shape)
             prog.run(x, y, ctx)
         else:
-            plan[i][0].apply(F.DeviceArray(x, x_chunk, x_dt),
-                             F.DeviceArray(y, out_info.chunk_shape, out_info.data_type), ctx=ctx)
+            ret = plan[i][0].apply(F.DeviceArray(x, x_chunk, x_dt),
+                                   F.DeviceArray(y, out_info.chunk_shape, out_info.data_type),
+                                   ctx=ctx)
         ctx.synchronize()
         t_k = time.perf_counter() - t1
         log(f"{i if j == i else f'{i}-{j}'}: {names} device-resident {list(x.shape)} {x_dt} -> "
             f"{list(y.shape)} {out_info.data_type} in {t_k:.3f}s")
+        components = None
+        if names in WHOLE_ARRAY:
+            components = int(ret)
+            log(f"   {components} components")
+            ctx.release_scratch()  # two index arrays: not held through the rest of the chain
         for k in range(i, j + 1):
             carrier = k == j
             st = {"wall_s": t_k if carrier else 0.0, "decode_s": t_read if k == 0 else 0.0,
@@ -720,6 +622,8 @@ def run_device_chain(steps: list, paths: list, device: int = 0, nthreads: int = 
             if j > i:
                 st["fused_into" if not carrier else "fused_steps"] = (
                     j if not carrier else list(range(i, j + 1)))
+            if components is not None:
+                st["components"] = components
             results.append(st)
         x, x_dt, x_chunk = y, out_info.data_type, out_info.chunk_shape
     t2 = time.perf_counter()
@@ -924,17 +828,29 @@ def run(steps: list, exists: str = "erase", tmp: str | None = None,
             params = {"operator": f.operator, "other": str(other)}
             log(f"{i}: arithmetic {f.operator} {src} ({info.data_type} {list(info.shape)}) "
                 f"with {other} -> {dst}")
+        elif name == "connected_components":
+            params = {"connectivity": f.connectivity}
+            log(f"{i}: connected_components connectivity={f.connectivity} "
+                f"{src} ({info.data_type} {list(info.shape)}) -> {dst}")
         else:
             params = {"stride": list(f.stride), "discrete": bool(step.get("discrete", False))}
             log(f"{i}: downsample stride={params['stride']} discrete={params['discrete']} "
                 f"{src} ({info.data_type} {list(info.shape)}) -> {dst}")
         params.update(data_type=step.get("data_type"), encoding=enc, chunk_limit=limit)
+
+        def whole_step(dev):  # the filters whose rows cannot be split: their own store function
+            if name == "connected_components":
+                return S.connected_components(src, dst, params["connectivity"],
+                                              data_type=params["data_type"], device=dev,
+                                              encoding=enc)
+            return S.summed_area_table(src, dst, data_type=params["data_type"], device=dev,
+                                       encoding=enc, chunk_limit=limit)
+
         if gpus > 1 and not rows_splittable(name):
             dev0 = (gpu_devices or [0])[0]
             log(f"   {name}: chunk rows depend on each other in order; one process on device "
                 f"{dev0}, not {gpus}")
-            st = S.summed_area_table(src, dst, data_type=params["data_type"], device=dev0,
-                                     encoding=enc, chunk_limit=limit)
+            st = whole_step(dev0)
         elif gpus > 1:
             st = run_rows_parallel(name, src, dst, params, out_shape, gpus, 0,
                                    devices=gpu_devices)
@@ -946,9 +862,8 @@ def run(steps: list, exists: str = "erase", tmp: str | None = None,
             st = S.gaussian(src, dst, params["sigma"], params["kernel_half_size"],
                             data_type=params["data_type"], device=device, encoding=enc,
                             chunk_limit=limit)
-        elif name == "summed_area_table":
-            st = S.summed_area_table(src, dst, data_type=params["data_type"], device=device,
-                                     encoding=enc, chunk_limit=limit)
+        elif not rows_splittable(name):
+            st = whole_step(device)
         elif name in RANK:
             st = S.rank_filter(src, dst, name, params["kernel_half_size"],
                                data_type=params["data_type"], device=device, encoding=enc,
@@ -964,6 +879,8 @@ def run(steps: list, exists: str = "erase", tmp: str | None = None,
             st = S.downsample(src, dst, params["stride"], discrete=params["discrete"],
                               data_type=params["data_type"], device=device, encoding=enc,
                               chunk_limit=limit)
+        if "components" in st:
+            log(f"   {st['components']} components")
         out = S.open_array(dst)
         log(f"   -> {out.data_type} {list(out.shape)} in {st['wall_s']:.2f}s "
             f"(rw:{st['decode_s']:.2f}/{st['encode_s']:.2f} p:{st['kernel_s']:.3f})")
