@@ -422,6 +422,41 @@ int zt_connected_components_apply_array(zt_ctx* ctx, int dtype_in, const void* i
                                         void* out, const int64_t* shape, int ndim,
                                         int connectivity, uint64_t* count);
 
+/* ---- exact Euclidean distance transform (an extension: the reference has no such filter) ------ */
+
+/* out[p] = the Euclidean distance from p to the nearest background element, or its square. The
+ * foreground rule is the labelling's: any bit set for bool and the integers, value != 0 for the
+ * four float types. spacing[a] >= 1 is the length of one step along axis a (NULL = all ones), and
+ *     d2(p) = min over background q of sum_a spacing[a]^2 * (p[a] - q[a])^2,
+ * an integer; 0 for a background element, +inf everywhere when the array has no background
+ * element; nothing wraps or replicates at the array edges. With squared == 0 the stored element is
+ * sqrt(d2 as f64) (correctly rounded) as TOut, the Rust `as` cast: saturating and truncating for
+ * integers, round-to-nearest-even for floats, +inf -> the type's maximum / +inf. With squared != 0
+ * it is d2 saturated at the maximum of an integer TOut, (d2 as f64) as TOut for a float TOut.
+ * With B = sum_a spacing[a]^2 * (shape[a] - 1)^2 the device works in uint32_t when B < 2^32 - 1
+ * and in uint64_t from there on (or with ZT_EDT_WORK64=1, read at every call); B >= 2^62, more
+ * than 2^38 elements or an extent >= 2^31 are ZT_ERR_INVALID_PARAMETERS, and so is a spacing
+ * below 1. Semantics and kernels: DESIGN.md §3.14. */
+/* An extension. All 13 types in; the 12 numeric types out (bool is
+ * ZT_ERR_UNSUPPORTED_DATA_TYPE). */
+int zt_distance_transform_is_compatible(int dtype_in, int dtype_out);
+/* An extension. Device bytes of one call: input + scratch + output,
+ *     n * (size(dtype_in) + size(dtype_out)) + n * (2 * W + 8),
+ * W = 4 or 8 the work width that shape, spacing and ZT_EDT_WORK64 select: two work arrays (an
+ * axis pass reads one and writes the other) and the apex and breakpoint stacks, 4 bytes per
+ * element each. 0 for an array with a zero extent. */
+int zt_distance_transform_memory(int dtype_in, int dtype_out, const int64_t* shape,
+                                 const int64_t* spacing /* NULL = ones */, int ndim,
+                                 uint64_t* bytes);
+/* An extension. Transforms the whole C-order device array `in` (shape[ndim], element alignment)
+ * into `out` (same shape, dtype_out, element alignment, not overlapping `in`) on the context's
+ * stream, without synchronising it. A refused scratch allocation is ZT_ERR_OUT_OF_MEMORY. A zero
+ * extent is a no-op. There is no per-chunk form: the nearest background element may lie in any
+ * chunk. */
+int zt_distance_transform_apply_array(zt_ctx* ctx, int dtype_in, const void* in, int dtype_out,
+                                      void* out, const int64_t* shape, const int64_t* spacing,
+                                      int ndim, int squared);
+
 /* ---- zarrs_info reductions (src/info/range.rs, src/info/histogram.rs) ------------------------ */
 
 /* The 12 numeric types; ZT_BOOL is ZT_ERR_UNSUPPORTED_DATA_TYPE (the reference reaches

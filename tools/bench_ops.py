@@ -30,6 +30,12 @@ connectivity 1 and 3 on sparse noise, dense noise and a thresholded synth_u16 vo
 with the Reencode uint8 -> uint32 cast of the same volume (the streaming floor); with scipy
 installed, scipy.ndimage.label on the host as the CPU baseline (`--no-scipy` skips it);
 `--cc-once` calls every labelling once and nothing else, for a kernel trace.
+`--only distance_transform`: the exact Euclidean distance transform (distance.hip) of 1024^3 uint8
+-> float32 on noise of density 0.5 and 0.999 and on a solid ball, at spacing (1, 1, 1) and
+(3, 1, 1), alternated with the Reencode uint8 -> float32 cast of the same volume (the streaming
+floor); with scipy installed and a volume of at most 512^3, scipy.ndimage.distance_transform_edt
+on the host as the CPU baseline (`--no-scipy` skips it); `--edt-once` calls every transform once
+and nothing else, for a kernel trace.
 
 Algorithmic bytes: pyramid = level 0 read once + every level written once (2 B per u16
 element; the fused launches never read an intermediate level back); Gaussian = 4 B read + 4 B written per voxel (the separable passes' intermediates are
@@ -904,6 +910,106 @@ def bench_connected_components(n, rounds=5, window_s=0.5, scipy_baseline=True, o
     return res
 
 
+def bench_distance_transform(n, rounds=5, window_s=0.5, scipy_baseline=True, once=False):
+    """The exact Euclidean distance transform on n^3 uint8 device arrays -> float32
+    (distance.hip) through DistanceTransform.apply, on noise of foreground density 0.5 (shallow
+    envelopes) and 0.999 (deep) and on one solid ball of radius 0.39 n (the worst-case stacks), at
+    spacing (1, 1, 1) and (3, 1, 1), alternated in one run with the Reencode uint8 -> float32 cast
+    of the same volume (one byte read and four written per element: the streaming floor, the
+    yardstick). Windows of at least window_s after a warm-up, `rounds` of each, medians. With
+    scipy installed and n <= 512, scipy.ndimage.distance_transform_edt on the host transforms
+    the same volumes (the CPU baseline; its float64 result as float32 is compared with the
+    device's). once=True: every transform called once, volume by volume, spacing ones then
+    (3, 1, 1), and nothing else (for a kernel trace)."""
+    import math
+    import numpy as np
+    import torch
+    import zarrs_tools_amd as zt
+    ctx = zt.default_context(0)
+    stream = torch.cuda.current_stream()
+    shape, total = (n, n, n), n ** 3
+    gen = torch.Generator(device="cuda").manual_seed(2025)
+    noise = torch.rand(shape, device="cuda", generator=gen)
+    ax = torch.arange(n, device="cuda", dtype=torch.float32) - (n - 1) / 2
+    r2 = ax[:, None, None] ** 2 + ax[None, :, None] ** 2 + ax[None, None, :] ** 2
+    volumes = {"noise_0.5": (noise < 0.5).to(torch.uint8),
+               "noise_0.999": (noise < 0.999).to(torch.uint8),
+               "ball": (r2 <= (0.39 * n) ** 2).to(torch.uint8)}
+    del noise, r2
+    out = torch.empty(shape, dtype=torch.float32, device="cuda")
+    cast = zt.PointwiseProgram([zt.Reencode()], "uint8", ["float32"], shape)
+    spacings = {"s111": (1, 1, 1), "s311": (3, 1, 1)}
+    filters = {k: zt.DistanceTransform(sp) for k, sp in spacings.items()}
+    chunk = (32, 32, 32)
+
+    def edt(v, k):
+        return filters[k].apply(zt.DeviceArray(v, chunk, "uint8"),
+                                zt.DeviceArray(out, chunk, "float32"), ctx=ctx)
+
+    if once:
+        for name, v in volumes.items():
+            for k in spacings:
+                edt(v, k)
+        torch.cuda.synchronize()
+        return {"op": "distance_transform, one call each",
+                "calls": [f"{name}_{k}" for name in volumes for k in spacings]}
+    ops = {}
+    for name, v in volumes.items():
+        ops[f"{name}_cast_u8_f32"] = (lambda v=v: cast.run(v, out, ctx))
+        for k in spacings:
+            ops[f"{name}_{k}"] = (lambda v=v, k=k: edt(v, k))
+    reps = {}
+    for k, fn in ops.items():  # warm-up, then calls per window until it lasts window_s
+        r = 1
+        while True:
+            t = timed(fn, stream, r)
+            if t * r >= window_s * 1e3:
+                break
+            r = math.ceil(window_s * 1e3 / t * 1.05) + 1
+        reps[k] = r
+    ms = {k: [] for k in ops}
+    for _ in range(rounds):
+        for k, fn in ops.items():
+            ms[k].append(timed(fn, stream, reps[k]))
+    res = {"op": "distance_transform uint8 -> float32 (device-resident)",
+           "config": {"shape": [n] * 3, "rounds": rounds, "window_s": window_s},
+           "foreground": {k: round(float(v.to(torch.float32).mean()), 4)
+                          for k, v in volumes.items()},
+           "memory_bytes": filters["s111"].memory("uint8", "float32", shape),
+           "ops": {}}
+    for k in ops:
+        v = sorted(ms[k])
+        med = v[len(v) // 2]
+        res["ops"][k] = {"ms": round(med, 4), "ms_min": round(v[0], 4), "ms_max": round(v[-1], 4),
+                         "spread": round((v[-1] - v[0]) / med, 4), "calls_per_window": reps[k],
+                         "ns_per_voxel": round(med * 1e6 / total, 5)}
+        if k.endswith("_cast_u8_f32"):
+            gbs = total * 5 / (med / 1e3) / 1e9
+            res["ops"][k].update({"GB/s": round(gbs, 1), "hbm_frac": round(gbs / HBM_PEAK_GBS, 4)})
+        else:
+            y = res["ops"][k.rsplit("_", 1)[0] + "_cast_u8_f32"]
+            res["ops"][k]["ratio_to_cast"] = round(med / y["ms"], 3)
+    if scipy_baseline and n <= 512:
+        try:
+            from scipy import ndimage
+        except ImportError:
+            ndimage = None
+        if ndimage is not None:
+            for name, v in volumes.items():
+                host = v.cpu().numpy()
+                for k, sp in spacings.items():
+                    t0 = time.perf_counter()
+                    want = ndimage.distance_transform_edt(host, sampling=sp)
+                    dt = time.perf_counter() - t0
+                    edt(v, k)
+                    got = out.cpu().numpy()
+                    o = res["ops"][f"{name}_{k}"]
+                    o["scipy_s"] = round(dt, 3)
+                    o["scipy_over_gpu"] = round(dt * 1e3 / o["ms"], 1)
+                    o["equals_scipy"] = bool(np.array_equal(got, want.astype(np.float32)))
+    return res
+
+
 def bench_guided4d(shape, chunk, radius, reps):
     """Config T per GPU: a (T, Z, Y, X) f32 time-series share, chunks
     (4, 256, 256, 256), eps 2500. 4-D arrays take the separable per-axis path."""
@@ -1011,9 +1117,13 @@ def main():
                     help="config T share: (t groups, z groups) of the 8-GPU split")
     ap.add_argument("--t-rank", type=int, default=None)
     ap.add_argument("--no-scipy", action="store_true",
-                    help="connected_components: skip the scipy.ndimage.label baseline")
+                    help="connected_components, distance_transform: skip the scipy.ndimage "
+                         "baseline on the host")
     ap.add_argument("--cc-once", action="store_true",
                     help="connected_components: call every labelling once, nothing else (for a "
+                         "kernel trace)")
+    ap.add_argument("--edt-once", action="store_true",
+                    help="distance_transform: call every transform once, nothing else (for a "
                          "kernel trace)")
     a = ap.parse_args()
     only = set(a.only.split(","))
@@ -1060,6 +1170,9 @@ def main():
     if "connected_components" in only:  # with the reencode uint8 -> uint32 yardstick, alternated
         print(json.dumps(bench_connected_components(
             a.gaussian_size, scipy_baseline=not a.no_scipy, once=a.cc_once)), flush=True)
+    if "distance_transform" in only:  # with the reencode uint8 -> float32 yardstick, alternated
+        print(json.dumps(bench_distance_transform(
+            a.gaussian_size, scipy_baseline=not a.no_scipy, once=a.edt_once)), flush=True)
 
 
 if __name__ == "__main__":

@@ -21,6 +21,7 @@ from .filter import (  # noqa: E402
     Context,
     Crop,
     DeviceArray,
+    DistanceTransform,
     Downsample,
     Equal,
     Gaussian,
@@ -65,4 +66,5 @@ __all__ = [
     "RankFilter", "Median", "Minimum", "Maximum",
     "Arithmetic", "ARITHMETIC_OPERATORS",
     "ConnectedComponents",
+    "DistanceTransform",
 ]

@@ -242,6 +242,10 @@ def lib() -> ctypes.CDLL:
         "zt_connected_components_memory": ([c_int, c_int, i64p, c_int, u64p], c_int),
         "zt_connected_components_apply_array": ([vp, c_int, vp, c_int, vp, i64p, c_int, c_int,
                                                  u64p], c_int),
+        "zt_distance_transform_is_compatible": ([c_int, c_int], c_int),
+        "zt_distance_transform_memory": ([c_int, c_int, i64p, i64p, c_int, u64p], c_int),
+        "zt_distance_transform_apply_array": ([vp, c_int, vp, c_int, vp, i64p, i64p, c_int,
+                                               c_int], c_int),
         "zt_range_is_compatible": ([c_int], c_int),
         "zt_histogram_is_compatible": ([c_int], c_int),
         "zt_range_init": ([vp, vp], c_int),

@@ -434,15 +434,6 @@ __global__ __launch_bounds__(kThreads) void cc_write_kernel(const IdxT* __restri
 
 // ---- host ----------------------------------------------------------------------------------------
 
-uint64_t fg_mask(int dtype) {
-    switch (dtype) {
-    case kBF16: case kF16: return 0x7FFFull;  // value != 0: every bit but the sign
-    case kF32: return 0x7FFFFFFFull;
-    case kF64: return 0x7FFFFFFFFFFFFFFFull;
-    default: return ~0ull;
-    }
-}
-
 // The backward half of the neighbourhood: offsets in {-1, 0, 1}^ndim whose first non-zero entry is
 // -1, with at most `connectivity` non-zero entries, none on an axis of extent 1.
 std::vector<CcOffset> backward_offsets(const int64_t* dim8, int ndim, int connectivity) {

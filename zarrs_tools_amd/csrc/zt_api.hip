@@ -21,6 +21,7 @@
 
 #include "../../include/zarrs_tools_amd.h"
 #include "zt_device.hpp"
+#include "zt_edt_host.hpp"
 #include "zt_kernels.hpp"
 
 namespace {
@@ -1661,6 +1662,85 @@ int zt_connected_components_apply_array(zt_ctx* ctx, int dtype_in, const void* i
     if (e != hipSuccess) return hip_fail(e, "connected components write launch");
     if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev1, ctx->cur));
     if (count) *count = k;
+    return ZT_OK;
+}
+
+// ---- exact Euclidean distance transform (an extension; distance.hip) -----------------------------
+
+static_assert(ZT_MAX_DIMS == zt::kEdtMaxDims, "zt_edt_host.hpp and the public header agree");
+
+namespace {
+
+// Shape, spacing and limits of a distance transform -> its plan (zt_edt_host.hpp).
+int edt_check(const int64_t* shape, const int64_t* spacing, int ndim, zt::EdtPlan* plan) {
+    if (int rc = check_shape(shape, ndim, "shape")) return rc;
+    switch (zt::edt_plan(shape, spacing, ndim, plan)) {
+    case zt::kEdtOk: return ZT_OK;
+    case zt::kEdtBadSpacing:
+        return fail(ZT_ERR_INVALID_PARAMETERS,
+                    "distance_transform: every spacing must be an integer >= 1");
+    case zt::kEdtBoundTooLarge:
+        return fail(ZT_ERR_INVALID_PARAMETERS,
+                    "distance_transform: the largest squared distance, the sum of spacing^2 * "
+                    "(extent - 1)^2, must be below 2^62");
+    case zt::kEdtTooManyElems:
+        return fail(ZT_ERR_INVALID_PARAMETERS,
+                    "distance_transform: the array has more than %lld elements",
+                    (long long)zt::kEdtMaxElems);
+    default:
+        return fail(ZT_ERR_INVALID_PARAMETERS,
+                    "distance_transform: every extent must be below 2^31");
+    }
+}
+
+}  // namespace
+
+int zt_distance_transform_is_compatible(int dtype_in, int dtype_out) {
+    for (int d : {dtype_in, dtype_out})
+        if (!valid_dtype(d))
+            return fail(ZT_ERR_UNSUPPORTED_DATA_TYPE, "Unsupported data type code %d", d);
+    if (dtype_out == ZT_BOOL)
+        return fail(ZT_ERR_UNSUPPORTED_DATA_TYPE,
+                    "distance_transform: distances need a numeric output type, not bool");
+    return ZT_OK;
+}
+
+int zt_distance_transform_memory(int dtype_in, int dtype_out, const int64_t* shape,
+                                 const int64_t* spacing, int ndim, uint64_t* bytes) {
+    if (int rc = zt_distance_transform_is_compatible(dtype_in, dtype_out)) return rc;
+    zt::EdtPlan plan;
+    if (int rc = edt_check(shape, spacing, ndim, &plan)) return rc;
+    if (!bytes) return fail(ZT_ERR_INVALID_PARAMETERS, "null pointer");
+    *bytes = plan.n == 0
+                 ? 0
+                 : (uint64_t)plan.n * (zt::dtype_size(dtype_in) + zt::dtype_size(dtype_out)) +
+                       zt::edt_scratch_bytes(plan.n, zt::edt_work64(plan.work64));
+    return ZT_OK;
+}
+
+int zt_distance_transform_apply_array(zt_ctx* ctx, int dtype_in, const void* in, int dtype_out,
+                                      void* out, const int64_t* shape, const int64_t* spacing,
+                                      int ndim, int squared) {
+    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = zt_distance_transform_is_compatible(dtype_in, dtype_out)) return rc;
+    zt::EdtPlan plan;
+    if (int rc = edt_check(shape, spacing, ndim, &plan)) return rc;
+    if (plan.n == 0) return ZT_OK;
+    if (!in || !out) return fail(ZT_ERR_INVALID_PARAMETERS, "null data pointer");
+    const uintptr_t a0 = (uintptr_t)in, a1 = a0 + (size_t)plan.n * zt::dtype_size(dtype_in);
+    const uintptr_t b0 = (uintptr_t)out, b1 = b0 + (size_t)plan.n * zt::dtype_size(dtype_out);
+    if (a0 < b1 && b0 < a1)
+        return fail(ZT_ERR_INVALID_PARAMETERS, "input and output must not overlap");
+    if ((a0 % zt::dtype_size(dtype_in)) != 0 || (b0 % zt::dtype_size(dtype_out)) != 0)
+        return fail(ZT_ERR_INVALID_PARAMETERS, "data pointers must be element aligned");
+    DeviceGuard guard(ctx->device);
+    const bool work64 = zt::edt_work64(plan.work64);
+    if (int rc = ctx->ensure_scratch((size_t)zt::edt_scratch_bytes(plan.n, work64))) return rc;
+    if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev0, ctx->cur));
+    hipError_t e = zt::launch_edt(in, dtype_in, shape, ndim, plan.weight, work64, ctx->scratch, out,
+                                  dtype_out, squared != 0, ctx->cur);
+    if (e != hipSuccess) return hip_fail(e, "distance transform launch");
+    if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev1, ctx->cur));
     return ZT_OK;
 }
 

@@ -257,4 +257,16 @@ inline size_t dtype_size(int code) {
     }
 }
 
+// The storage bits that make an element foreground (non-zero) for the labelling and the distance
+// transform: any bit for bool and the integers, every bit but the sign for the
+// float types (+-0.0 are background; NaNs, subnormals and infinities are foreground).
+inline uint64_t fg_mask(int dtype) {
+    switch (dtype) {
+    case kBF16: case kF16: return 0x7FFFull;  // value != 0: every bit but the sign
+    case kF32: return 0x7FFFFFFFull;
+    case kF64: return 0x7FFFFFFFFFFFFFFFull;
+    default: return ~0ull;
+    }
+}
+
 }  // namespace zt

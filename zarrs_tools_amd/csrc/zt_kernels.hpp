@@ -277,6 +277,18 @@ hipError_t launch_cc_label(const void* in, int dtype_in, const int64_t* shape, i
 hipError_t launch_cc_write(const void* scratch, int64_t n, bool idx64, void* out, int dtype_out,
                            hipStream_t s);
 
+// The exact Euclidean distance transform (distance.hip; an extension, no reference filter;
+// DESIGN.md §3.14) of a contiguous C-order array of `shape` at element alignment: out = sqrt(d2)
+// as dtype_out, or d2 itself with `squared`, d2 the squared distance to the nearest background
+// (zero) element with `weight[a]` = spacing_a^2 per axis (zt_edt_host.hpp's edt_plan computes the
+// weights, the bound B and whether it needs 64-bit work elements). Scratch (edt_scratch_bytes):
+// two work arrays of n elements and the two stacks of n 4-byte slots. edt_work64 ORs the
+// ZT_EDT_WORK64=1 switch into what B needs. Everything runs on `s`; nothing synchronises.
+bool edt_work64(bool needed);
+hipError_t launch_edt(const void* in, int dtype_in, const int64_t* shape, int ndim,
+                      const uint64_t* weight, bool work64, void* scratch, void* out, int dtype_out,
+                      int squared, hipStream_t s);
+
 // zarrs_info reductions (info.hip; src/info/range.rs, src/info/histogram.rs) over a contiguous
 // run of n elements of `dtype` (the 12 numeric types) at element alignment.
 // Range: `state` is two device u64 words (smallest key, largest key) that accumulate across

@@ -25,6 +25,8 @@ Names, argument meaning and error behaviour follow LDeakin/zarrs_tools 0.7.2:
     its semantics are DESIGN.md §3.12
   - ``ConnectedComponents``: an extension with no counterpart in the reference (labels of the
     connected sets of non-zero elements); its semantics are DESIGN.md §3.13
+  - ``DistanceTransform``: an extension with no counterpart in the reference (the exact Euclidean
+    distance to the nearest zero element); its semantics are DESIGN.md §3.14
   - ``chunk_occupancy`` <- zarrs' ``store_empty_chunks = false`` (which chunks of a device
     array hold anything but the fill value)
   - ``ArraySubsetOverlap`` <- src/filter/array_subset_overlap.rs:4-52
@@ -1384,6 +1386,96 @@ class ConnectedComponents:
         """The filter's `apply` over device-resident arrays; returns K."""
         x, dtype_in = _info_run(input)
         return self._run(x, dtype_in, output.data, output.dtype, ctx)
+
+
+def distance_transform_default_type(squared: bool) -> str:
+    """float32 distances, uint32 squared distances (exact integers)."""
+    return "uint32" if squared else "float32"
+
+
+class DistanceTransform:
+    """An extension with no counterpart in the reference: the exact Euclidean
+    distance of every element to the nearest background element, background being what the
+    labelling calls background (zero bits for bool and the integers, value == 0 for the floats).
+    `spacing` is one integer >= 1 per axis, the length of a step along it (default all 1), and
+    d2(p) = min over background q of sum_a spacing_a^2 (p_a - q_a)^2 is an integer: +inf everywhere
+    when the array has no background. The output is sqrt(d2 as f64) as TOut (default float32),
+    or with `squared` d2 itself (default uint32; saturated at an integer type's maximum, (d2 as
+    f64) as TOut for a float type). All 13 types in, the 12 numeric types out. The transform is a
+    whole-array operation (the nearest background may lie in any chunk): no per-chunk form."""
+
+    def __init__(self, spacing=None, squared: bool = False):
+        self.squared = bool(squared)
+        self.spacing = None
+        if spacing is not None:
+            vals = []
+            for s in spacing:
+                try:
+                    ok = not isinstance(s, bool) and int(s) == s and int(s) >= 1
+                except (TypeError, ValueError):
+                    ok = False
+                if not ok:
+                    raise _invalid(f"distance_transform: spacing {s!r} is not an integer >= 1")
+                vals.append(int(s))
+            self.spacing = tuple(vals)
+
+    def name(self) -> str:
+        return "distance transform"
+
+    def check_spacing(self, ndim: int) -> None:
+        """InvalidParameters unless the spacing has one entry per axis (or is the default)."""
+        if self.spacing is not None and len(self.spacing) != int(ndim):
+            raise _invalid(f"distance_transform: spacing {list(self.spacing)} has "
+                           f"{len(self.spacing)} entries for an array of rank {int(ndim)}")
+
+    def _spacing_arg(self):
+        return i64_array(self.spacing) if self.spacing is not None else None
+
+    def is_compatible(self, dtype_in: str, dtype_out: str) -> None:
+        check(lib().zt_distance_transform_is_compatible(_info_dtype(dtype_in),
+                                                        _info_dtype(dtype_out)))
+
+    def memory(self, dtype_in: str, dtype_out: str, shape) -> int:
+        """Device bytes of one call on an array of `shape`: input + scratch + output."""
+        self.check_spacing(len(shape))
+        out = ctypes.c_uint64()
+        check(lib().zt_distance_transform_memory(
+            _info_dtype(dtype_in), _info_dtype(dtype_out), i64_array(shape), self._spacing_arg(),
+            len(shape), ctypes.byref(out)))
+        return int(out.value)
+
+    def _run(self, x, dtype_in, out, dtype_out, ctx) -> None:
+        if tuple(out.shape) != tuple(x.shape):
+            raise _invalid(f"Array shapes do not match: {list(x.shape)} vs {list(out.shape)}")
+        if x.device != out.device:
+            raise _invalid("distance_transform: the arrays are on different devices")
+        if not out.is_contiguous():
+            raise _invalid("distance_transform: the output must be contiguous")
+        self.is_compatible(dtype_in, dtype_out)
+        self.check_spacing(x.dim())
+        ctx = ctx or default_context(x.device.index)
+        check(lib().zt_distance_transform_apply_array(
+            ctx.handle, DTYPES[dtype_in], _ptr(x), DTYPES[dtype_out], _ptr(out),
+            i64_array(x.shape), self._spacing_arg(), x.dim(), int(self.squared)))
+
+    def apply_ndarray(self, v, dtype_out: Optional[str] = None, ctx: Optional[Context] = None,
+                      out=None):
+        """Transforms a device tensor; returns a new tensor of `dtype_out` (default float32, or
+        uint32 with `squared`), or `out` (contiguous, of `dtype_out`, not overlapping the input)."""
+        x, dtype_in = _info_run(v)
+        dtype_out = dtype_out or (dtype_of(out) if out is not None
+                                  else distance_transform_default_type(self.squared))
+        if out is None:
+            self.is_compatible(dtype_in, dtype_out)
+            out = _torch().empty(tuple(x.shape), dtype=torch_dtype(dtype_out), device=x.device)
+        self._run(x, dtype_in, out, dtype_out, ctx)
+        return out
+
+    def apply(self, input: DeviceArray, output: DeviceArray,
+              ctx: Optional[Context] = None) -> None:
+        """The filter's `apply` over device-resident arrays."""
+        x, dtype_in = _info_run(input)
+        self._run(x, dtype_in, output.data, output.dtype, ctx)
 
 
 class Downsample:

@@ -496,31 +496,46 @@ def connected_components(input_path, output_path, connectivity: int = 1,
     writes no chunk and publishes no zarr.json. Returns the run stats and "components": K."""
     import time
     from . import filter as F
-    from .device_io import _read_pieces, _row_spans, read_to_device, write_from_device
     t0 = time.perf_counter()
     info = open_array(input_path)
     filt = F.ConnectedComponents(connectivity)
     dt, enc = connected_components_output(data_type, encoding)
     filt.is_compatible(info.data_type, dt)
     filt.check_connectivity(info.ndim)
+    st, k = _whole_array_step(
+        input_path, output_path, info, filt, dt, enc, device, nthreads, t0,
+        "input, labels and two index arrays",
+        "connected_components labels the whole array in device memory (a component "
+        "may span every chunk): there is no store -> store path to fall back to")
+    st["components"] = int(k)
+    return st
+
+
+def _whole_array_step(input_path, output_path, info, filt, dt, enc, device, nthreads, t0,
+                      terms: str, no_fallback: str):
+    """A filter whose unit of work is the whole array (connected_components, distance_transform):
+    budgets checked before anything is read, the metadata held back, the array read into device
+    memory, `filt.apply` on it, the result written once, the metadata published. Returns (run
+    stats, what `filt.apply` returned)."""
+    import time
+    from . import filter as F
+    from .device_io import _read_pieces, _row_spans, read_to_device, write_from_device
     for name in ("zarr.json", PENDING_METADATA):  # the output is not finished until the end
         try:
             os.remove(os.path.join(output_path, name))
         except FileNotFoundError:
             pass
-    # budgets, before anything is read: the array, its labels and the scratch on the device; the
+    # budgets, before anything is read: the array, its result and the scratch on the device; the
     # pinned pieces of the read and the pinned rows of the write on the host
     shape = [int(s) for s in info.shape]
     in_esz, out_esz = NUMPY[info.data_type]().itemsize, NUMPY[dt]().itemsize
     need = filt.memory(info.data_type, dt, shape)
     budget = device_available_bytes(device) // 10 * 8
-    no_fallback = ("connected_components labels the whole array in device memory (a component "
-                   "may span every chunk): there is no store -> store path to fall back to")
     if need > budget:
         raise _abi.FilterError(
             _abi.ERR_OUT_OF_MEMORY,
             "There is not enough available memory to process the array: it needs "
-            f"{need} bytes of device memory (input, labels and two index arrays) and 80 % of "
+            f"{need} bytes of device memory ({terms}) and 80 % of "
             f"the available memory is {budget}; {no_fallback}")
     host_need = 0
     if all(s > 0 for s in shape):
@@ -550,8 +565,8 @@ def connected_components(input_path, output_path, connectivity: int = 1,
     ctx = F.default_context(device)
     t1 = time.perf_counter()
     try:
-        k = filt.apply(F.DeviceArray(x, info.chunk_shape, info.data_type),
-                       F.DeviceArray(y, out_info.chunk_shape, dt), ctx=ctx)
+        ret = filt.apply(F.DeviceArray(x, info.chunk_shape, info.data_type),
+                         F.DeviceArray(y, out_info.chunk_shape, dt), ctx=ctx)
         ctx.synchronize()
     finally:
         ctx.release_scratch()
@@ -566,7 +581,48 @@ def connected_components(input_path, output_path, connectivity: int = 1,
             "h2d_s": 0.0, "kernel_s": t_kernel, "d2h_s": 0.0, "bytes_read": n * in_esz,
             "bytes_written": n * out_esz, "voxels": n, "rows": 0, "threads": int(nthreads),
             "rows_in_flight": 0, "double_buffered": 0, "chunks_elided": int(elided),
-            "device_resident": True, "components": int(k)}
+            "device_resident": True}, ret
+
+
+def distance_transform_output(squared: bool = False, data_type: Optional[str] = None,
+                              encoding=None):
+    """(output data type, encoding) of a distance transform's output array: an explicit data
+    type (`data_type` or the encoding's) wins, else float32, or uint32 for squared distances; the
+    fill value is 0 unless given."""
+    from .filter import distance_transform_default_type
+    enc = dict(encoding) if isinstance(encoding, dict) else (
+        json.loads(encoding) if encoding else {})
+    dt = enc.get("data_type") or data_type or distance_transform_default_type(squared)
+    enc["data_type"] = dt
+    if enc.get("fill_value") is None:
+        enc["fill_value"] = 0
+    return dt, enc
+
+
+def distance_transform(input_path, output_path, spacing=None, squared: bool = False,
+                       data_type: Optional[str] = None, device: int = 0, nthreads: int = 0,
+                       encoding=None) -> dict:
+    """zarrs_filter distance-transform INPUT OUTPUT [--spacing S[,S...]] [--squared]
+    [--data-type T]: the exact Euclidean distance of every element to the nearest zero element
+    (filter.DistanceTransform; float32, or uint32 with `squared`, and fill value 0 unless given).
+    The nearest background element may lie in any chunk, so the whole array is read into device
+    memory, transformed there and written once; there is no store -> store path, and an array that
+    does not fit 80 % of the free device memory fails with ZT_ERR_OUT_OF_MEMORY before anything is
+    read. Returns the run stats."""
+    import time
+    from . import filter as F
+    t0 = time.perf_counter()
+    info = open_array(input_path)
+    filt = F.DistanceTransform(spacing, squared)
+    dt, enc = distance_transform_output(squared, data_type, encoding)
+    filt.is_compatible(info.data_type, dt)
+    filt.check_spacing(info.ndim)
+    st, _ = _whole_array_step(
+        input_path, output_path, info, filt, dt, enc, device, nthreads, t0,
+        "input, distances, two work arrays and two stacks",
+        "distance_transform works on the whole array in device memory (the nearest background "
+        "element may lie in any chunk): there is no store -> store path to fall back to")
+    return st
 
 
 def pointwise_output(filt, input_data_type: str, data_type: Optional[str] = None, encoding=None):

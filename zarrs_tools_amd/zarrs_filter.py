@@ -1,7 +1,7 @@
 """``zarrs_filter`` for the on-path filters (guided_filter, downsample, gaussian,
 summed_area_table, the rank filters median, minimum, maximum, the per-element reencode, crop,
 rescale, clamp, equal, replace_value, the two-array arithmetic and the whole-array
-connected_components) over Zarr V3 stores.
+connected_components and distance_transform) over Zarr V3 stores.
 
 Mirrors src/bin/zarrs_filter.rs (LDeakin/zarrs_tools 0.7.2) for the filters this framework
 accelerates:
@@ -20,7 +20,9 @@ accelerates:
                                         | replace-value IN OUT VALUE REPLACE
                                         | arithmetic IN OUT OPERATOR OTHER [--data-type T]
                                         | connected-components IN OUT [--connectivity C]
-                                              [--data-type T]]
+                                              [--data-type T]
+                                        | distance-transform IN OUT [--spacing S[,S...]]
+                                              [--squared] [--data-type T]]
 
 * subcommand arguments as GuidedFilterArguments (guided_filter.rs:25-33),
   DownsampleArguments (downsample.rs:20-33, STRIDE comma delimited) and GaussianArguments
@@ -43,10 +45,18 @@ accelerates:
   most 1 on every axis and on at most C axes (--connectivity, default 1: faces); OUT is uint32
   with fill value 0 unless --data-type names another integer type, and the step fails, writing
   nothing, when K does not fit it; the step logs K;
+  distance-transform (an extension: the reference has none) gives every element
+  its exact Euclidean distance to the nearest zero element (0 on the background, +inf, or the
+  type's maximum, everywhere when there is none); --spacing is the length of a step along each
+  axis, comma delimited integers >= 1, one per axis (default all 1); --squared stores the squared
+  distance, an exact integer; OUT is float32 (uint32 with --squared) with fill value 0 unless
+  --data-type names another numeric type;
 * a JSON run config is a list of {"filter": "guided_filter" | "downsample" | "gaussian" |
   "summed_area_table" | "median" | "minimum" | "maximum" | "reencode" | "crop" | "rescale" |
-  "clamp" | "equal" | "replace_value" | "arithmetic" | "connected_components", "input", "output", ...args (kernel_half_size; offset, shape, multiply, add, add_first, min, max, value, replace
-  for the per-element filters; connectivity for connected_components; operator, other for
+  "clamp" | "equal" | "replace_value" | "arithmetic" | "connected_components" |
+  "distance_transform", "input", "output", ...args (kernel_half_size; offset, shape, multiply, add, add_first, min, max, value, replace
+  for the per-element filters; connectivity for connected_components; spacing, squared for
+  distance_transform; operator, other for
   arithmetic, whose "other" is a path or the
   "$name" of a temporary that an earlier step wrote), "data_type"}, with "$name" meaning a named
   temporary array under --tmp and an omitted input meaning the previous filter's output (zarrs_filter.rs:106-138,
@@ -63,6 +73,8 @@ accelerates:
   arithmetic step reads as its "other" is written to the store by the step that produces it;
   a connected_components step may be part of such a chain (equal -> connected_components labels
   a mask that never touches the store), and the chain's budget then counts its two index arrays;
+  so may a distance_transform step (equal -> distance_transform -> clamp erodes a mask by a ball),
+  whose work arrays and stacks the budget counts in the same way;
 * every filter takes the reencoding arguments (ZarrReencodingArgs, lib.rs:274-377: -d/--data-type,
   -f/--fill-value, --separator, -c/--chunk-shape, -s/--shard-shape, --array-to-array-codecs,
   --array-to-bytes-codec, --bytes-to-bytes-codecs, --dimension-names, --attributes,
@@ -76,10 +88,10 @@ accelerates:
 
 gradient_magnitude is rejected with FilterError::Other: it runs from the library only
 (DESIGN.md §1). A summed-area table's chunk rows each need the previous row's last plane, so with
---gpus > 1 that step runs in one process on the first device (`rows_splittable`); so does
-connected_components, whose unit of work is the whole array: it is read into device memory,
-labelled and written once, and fails with the out-of-memory error when it does not fit (there is
-no store -> store path for it). The other
+--gpus > 1 that step runs in one process on the first device (`rows_splittable`); so do
+connected_components and distance_transform, whose unit of work is the whole array: it is read
+into device memory, processed and written once, and fails with the out-of-memory error when it
+does not fit (there is no store -> store path for them). The other
 filters' rows, the per-element ones included, are split over the processes. `--chunk-limit N`
 bounds the chunks in flight (decoded input rows + output rows being computed or encoded, and the
 host worker threads) at N, down to the pipeline's unit of one slab and one output row
@@ -107,7 +119,8 @@ from .device_io import _read_pieces, _row_spans, read_to_device, write_from_devi
 POINTWISE = ("reencode", "crop", "rescale", "clamp", "equal", "replace_value")
 RANK = ("median", "minimum", "maximum")
 BINARY = ("arithmetic",)  # two arrays in: "input" and "other"
-WHOLE_ARRAY = ("connected_components",)  # no chunk rows at all: the array is the unit of work
+# no chunk rows at all: the array is the unit of work
+WHOLE_ARRAY = ("connected_components", "distance_transform")
 ON_PATH = ("guided_filter", "downsample", "gaussian", "summed_area_table") + RANK + POINTWISE + \
     BINARY + WHOLE_ARRAY
 
@@ -115,8 +128,9 @@ ON_PATH = ("guided_filter", "downsample", "gaussian", "summed_area_table") + RAN
 def rows_splittable(name: str) -> bool:
     """Whether a store step's output chunk rows are independent, so that --gpus > 1 may split
     them over processes. A summed-area table's rows are not: each row's axis-0 sum starts from
-    the previous row's last plane (summed_area_table.rs:69, :94-97). Nor are a labelling's: a
-    connected component may span every chunk."""
+    the previous row's last plane (summed_area_table.rs:69, :94-97). Nor are a labelling's or a
+    distance transform's: a connected component may span every chunk, and the nearest background
+    element may lie in any."""
     return name != "summed_area_table" and name not in WHOLE_ARRAY
 
 
@@ -292,6 +306,16 @@ def build_parser() -> argparse.ArgumentParser:
                     help="neighbours differ on at most this many axes (1: faces, the default; "
                          "the rank: the full neighbourhood)")
     _add_reencode_args(cc)
+    dtr = sub.add_parser("distance-transform",
+                         help="Exact Euclidean distance to the nearest zero element.")
+    dtr.add_argument("input")
+    dtr.add_argument("output")
+    dtr.add_argument("--spacing", type=_parse_stride, default=None,
+                     help="the length of a step along each axis: comma delimited integers >= 1, "
+                          "one per axis (default: all 1)")
+    dtr.add_argument("--squared", action="store_true",
+                     help="store the squared distance (an exact integer; uint32 by default)")
+    _add_reencode_args(dtr)
     return ap
 
 
@@ -331,6 +355,10 @@ def _steps_from_cli(a) -> list:
     if a.filter == "connected-components":
         return [{"filter": "connected_components", "input": a.input, "output": a.output,
                  "connectivity": a.connectivity, "data_type": a.data_type,
+                 "chunk_limit": a.filter_chunk_limit, **_reencode_of(a)}]
+    if a.filter == "distance-transform":
+        return [{"filter": "distance_transform", "input": a.input, "output": a.output,
+                 "spacing": a.spacing, "squared": a.squared, "data_type": a.data_type,
                  "chunk_limit": a.filter_chunk_limit, **_reencode_of(a)}]
     return []
 
@@ -426,8 +454,11 @@ def step_encoding(step: dict, in_data_type: str):
     if step.get("filter") in POINTWISE:
         _dt, enc = S.pointwise_output(pointwise_filter(step), in_data_type,
                                       step.get("data_type"), enc)
-    if step.get("filter") in WHOLE_ARRAY:  # labels: uint32, fill value 0
+    if step.get("filter") == "connected_components":  # labels: uint32, fill value 0
         _dt, enc = S.connected_components_output(step.get("data_type"), enc)
+    if step.get("filter") == "distance_transform":  # float32, or uint32 squared; fill value 0
+        _dt, enc = S.distance_transform_output(bool(step.get("squared", False)),
+                                               step.get("data_type"), enc)
     return enc
 
 
@@ -440,6 +471,24 @@ def connectivity_of(step: dict) -> int:
         raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS,
                                      f"connected_components: connectivity {c!r} is not an "
                                      "integer") from None
+
+
+def distance_transform_of(step: dict):
+    """The DistanceTransform of a run-config step: "spacing" a list (or a comma delimited string)
+    of integers >= 1, default all 1; "squared" a boolean, default false."""
+    from . import filter as F
+    sp = step.get("spacing")
+    if isinstance(sp, str):
+        sp = [x.strip() for x in sp.split(",") if x.strip()]
+        try:
+            sp = [int(x) for x in sp]
+        except ValueError:
+            raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS,
+                                         f"distance_transform: spacing {step['spacing']!r} is "
+                                         "not a list of integers") from None
+    elif sp is not None and not isinstance(sp, (list, tuple)):
+        sp = [sp]
+    return F.DistanceTransform(sp, bool(step.get("squared", False)))
 
 
 def _step_params(step, info):
@@ -458,6 +507,14 @@ def _step_params(step, info):
         dt, _enc = S.connected_components_output(step.get("data_type"), encoding_of(step))
         f.is_compatible(info.data_type, dt)
         f.check_connectivity(info.ndim)
+        return f, tuple(info.shape), dt
+    if name == "distance_transform":
+        f = distance_transform_of(step)
+        dt, _enc = S.distance_transform_output(f.squared, step.get("data_type"),
+                                               encoding_of(step))
+        f.is_compatible(info.data_type, dt)
+        f.check_spacing(info.ndim)
+        f.memory(info.data_type, dt, info.shape)  # the bound on the squared distance
         return f, tuple(info.shape), dt
     dt = step.get("data_type") or (encoding_of(step) or {}).get("data_type") or info.data_type
     if name == "guided_filter":
@@ -556,7 +613,8 @@ def run_device_chain(steps: list, paths: list, device: int = 0, nthreads: int = 
     # only the arrays that are materialised count: each launch's input and output
     peak = max(_nbytes(plan[i][1].shape, plan[i][1].data_type) + _nbytes(plan[j][2], plan[j][3])
                for i, j in groups)
-    # a labelling's scratch (two index arrays) is larger than its input + output: count it
+    # a whole-array step's scratch (the labelling's two index arrays, the distance transform's
+    # work arrays and stacks) is larger than its input + output: count it
     whole = max([plan[k][0].memory(plan[k][1].data_type, plan[k][3], plan[k][2])
                  for k, st in enumerate(steps) if st.get("filter") in WHOLE_ARRAY], default=0)
     free, _total = torch.cuda.mem_get_info(device)
@@ -608,10 +666,11 @@ def run_device_chain(steps: list, paths: list, device: int = 0, nthreads: int = 
         log(f"{i if j == i else f'{i}-{j}'}: {names} device-resident {list(x.shape)} {x_dt} -> "
             f"{list(y.shape)} {out_info.data_type} in {t_k:.3f}s")
         components = None
-        if names in WHOLE_ARRAY:
+        if names == "connected_components":  # only the labelling has a count
             components = int(ret)
             log(f"   {components} components")
-            ctx.release_scratch()  # two index arrays: not held through the rest of the chain
+        if names in WHOLE_ARRAY:
+            ctx.release_scratch()  # whole-array scratch: not held through the rest of the chain
         for k in range(i, j + 1):
             carrier = k == j
             st = {"wall_s": t_k if carrier else 0.0, "decode_s": t_read if k == 0 else 0.0,
@@ -832,6 +891,11 @@ def run(steps: list, exists: str = "erase", tmp: str | None = None,
             params = {"connectivity": f.connectivity}
             log(f"{i}: connected_components connectivity={f.connectivity} "
                 f"{src} ({info.data_type} {list(info.shape)}) -> {dst}")
+        elif name == "distance_transform":
+            params = {"spacing": None if f.spacing is None else list(f.spacing),
+                      "squared": f.squared}
+            log(f"{i}: distance_transform spacing={params['spacing'] or 'ones'} "
+                f"squared={f.squared} {src} ({info.data_type} {list(info.shape)}) -> {dst}")
         else:
             params = {"stride": list(f.stride), "discrete": bool(step.get("discrete", False))}
             log(f"{i}: downsample stride={params['stride']} discrete={params['discrete']} "
@@ -843,6 +907,10 @@ def run(steps: list, exists: str = "erase", tmp: str | None = None,
                 return S.connected_components(src, dst, params["connectivity"],
                                               data_type=params["data_type"], device=dev,
                                               encoding=enc)
+            if name == "distance_transform":
+                return S.distance_transform(src, dst, params["spacing"], params["squared"],
+                                            data_type=params["data_type"], device=dev,
+                                            encoding=enc)
             return S.summed_area_table(src, dst, data_type=params["data_type"], device=dev,
                                        encoding=enc, chunk_limit=limit)
 
