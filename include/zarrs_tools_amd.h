@@ -457,6 +457,86 @@ int zt_distance_transform_apply_array(zt_ctx* ctx, int dtype_in, const void* in,
                                       void* out, const int64_t* shape, const int64_t* spacing,
                                       int ndim, int squared);
 
+/* ---- per-label statistics and the label size filter (extensions: no reference operation) ------ */
+
+/* A label array holds 0 for background and 1 .. K for objects (what zt_connected_components
+ * writes). The statistics are a reduction keyed by label into a device `state` of u64 words,
+ * struct-of-arrays over K + 1 rows: column c of label l is word c * (K + 1) + l (row 0, the
+ * background, is never written).
+ *   column 0                  count: the elements of the label
+ *   columns 1 + 3a .. 3 + 3a  on axis a: the smallest coordinate, the largest (inclusive) and the
+ *                             sum of the coordinates, coordinates being those of the whole array
+ *                             (origin + index in the box)
+ *   with an intensity array, after the ndim axes:
+ *   column 1 + 3 ndim         the smallest orderable key of the label's non-NaN intensities
+ *   column 2 + 3 ndim         the largest
+ *   columns 3, 4 + 3 ndim     the sum of the intensities as a 128-bit two's complement integer
+ *                             (lo, hi), kept for the six integer types of up to 32 bits
+ *   word cols * (K + 1)       the number of label elements outside [0, K]
+ * An absent label has count 0, minima of all ones and maxima of 0; a label with no non-NaN
+ * intensity has a smallest key above its largest. The key of an element is its storage bits
+ * (zero-extended) for the unsigned types, with the sign bit flipped for the signed ones, and for the
+ * float types the bits with the sign bit set when it was clear and all bits flipped when it was
+ * set: keys order as the values do, -0.0 below +0.0, the infinities as values. Every column is an
+ * integer sum, minimum or maximum: the state does not depend on the launch geometry, and
+ * accumulating two halves of an array equals accumulating the whole. Limits, all
+ * ZT_ERR_INVALID_PARAMETERS: K in [0, 2^31 - 2]; at most 2^38 elements in a box; origin >= 0;
+ * elements * (largest origin + extent) < 2^64, so that no coordinate sum wraps. Semantics and
+ * kernels: DESIGN.md §3.15. */
+#define ZT_NO_DTYPE (-1) /* dtype_intensity of a call without an intensity array */
+/* The rows of a tile of the statistics kernel (a tile is ZT_LABELS_TILE_ROWS rows x 64 x). */
+#define ZT_LABELS_TILE_ROWS 16
+/* An extension. Labels: the eight integer types; intensity: ZT_NO_DTYPE or the 12 numeric types
+ * (anything else is ZT_ERR_UNSUPPORTED_DATA_TYPE). */
+int zt_label_statistics_is_compatible(int dtype_labels, int dtype_intensity);
+/* An extension. Bytes of the state: 8 * ((1 + 3 ndim + (with_intensity ? 4 : 0)) * (K + 1) + 1). */
+int zt_label_statistics_state_bytes(int ndim, int64_t n_labels, int with_intensity,
+                                    uint64_t* bytes);
+/* An extension. Fills `state` (device memory, 8-byte aligned) with the empty state on the
+ * context's stream. */
+int zt_label_statistics_init(zt_ctx* ctx, int ndim, int64_t n_labels, int with_intensity,
+                             void* state);
+/* An extension. Folds the contiguous C-order device box `labels` (box_shape[ndim], element
+ * alignment) that lies at `origin` (NULL = zeros) of the whole array into `state` on the context's
+ * stream, without synchronising it. `intensity` (same shape, dtype_intensity, element alignment)
+ * goes with a state that was sized and initialised with_intensity; NULL with ZT_NO_DTYPE
+ * otherwise. An element below 0 or above n_labels is counted in the state's last word and changes
+ * nothing else. A zero extent is a no-op. The grid is capped (ZT_LABELS_MAX_BLOCKS lowers the cap,
+ * ZT_LABELS_LDS_SLOTS the slots of a workgroup's table; both are read at every call). */
+int zt_label_statistics_accumulate(zt_ctx* ctx, int dtype_labels, const void* labels,
+                                   int dtype_intensity, const void* intensity,
+                                   const int64_t* box_shape, const int64_t* origin, int ndim,
+                                   int64_t n_labels, void* state);
+/* An extension. Waits for the stream and copies the state into host_state (host memory of
+ * zt_label_statistics_state_bytes; may be NULL). When elements outside [0, K] were counted the
+ * call fails with ZT_ERR_INVALID_PARAMETERS (`label_statistics: N elements outside [0, K]`);
+ * *invalid (may be NULL) receives N either way. */
+int zt_label_statistics_finish(zt_ctx* ctx, const void* state, int ndim, int64_t n_labels,
+                               int with_intensity, uint64_t* host_state, uint64_t* invalid);
+
+/* The label size filter: a label whose count lies in [min_size, max_size] is kept, every other
+ * label becomes 0. With relabel != 0 the kept labels are renumbered 1 .. K' in increasing order of
+ * their old value (so the output of zt_connected_components stays numbered in the C order of first
+ * elements); otherwise they keep their values. *kept receives K', the number of labels kept. */
+/* An extension. The eight integer types in and out. */
+int zt_label_size_filter_is_compatible(int dtype_in, int dtype_out);
+/* An extension. Device bytes of one call on an array whose largest label is n_labels: input +
+ * scratch + output, n * (size(dtype_in) + size(dtype_out)) + 8 * (K + 2) +
+ * round_up(4 * (K + 1), 8) + 16 (the counts and their trailing word, the remap table, K' and the
+ * largest label kept). 0 for an array with a zero extent. */
+int zt_label_size_filter_memory(int dtype_in, int dtype_out, const int64_t* shape, int ndim,
+                                int64_t n_labels, uint64_t* bytes);
+/* An extension. Filters the whole C-order device array `in` (shape[ndim], element alignment) into
+ * `out` (same shape, dtype_out, element alignment, not overlapping `in`) on the context's stream.
+ * min_size < 1, max_size < min_size (max_size < 0 = no upper bound), a negative element, a
+ * largest label above 2^31 - 2 and a largest output label that does not fit dtype_out are
+ * ZT_ERR_INVALID_PARAMETERS, all before `out` is written. The call synchronises the stream twice:
+ * to read the largest label, then K' and the check of the elements. A zero extent is a no-op with
+ * K' = 0. */
+int zt_label_size_filter_apply_array(zt_ctx* ctx, int dtype_in, const void* in, int dtype_out,
+                                     void* out, const int64_t* shape, int ndim, int64_t min_size,
+                                     int64_t max_size, int relabel, uint64_t* kept);
+
 /* ---- zarrs_info reductions (src/info/range.rs, src/info/histogram.rs) ------------------------ */
 
 /* The 12 numeric types; ZT_BOOL is ZT_ERR_UNSUPPORTED_DATA_TYPE (the reference reaches

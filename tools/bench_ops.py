@@ -30,6 +30,9 @@ connectivity 1 and 3 on sparse noise, dense noise and a thresholded synth_u16 vo
 with the Reencode uint8 -> uint32 cast of the same volume (the streaming floor); with scipy
 installed, scipy.ndimage.label on the host as the CPU baseline (`--no-scipy` skips it);
 `--cc-once` calls every labelling once and nothing else, for a kernel trace.
+`--only label_statistics`: the per-label statistics and the label size filter (labels.hip) on
+1024^3 uint32 labels (the labelling's three volumes at connectivity 1, the dense one at 3 as well),
+alternated with Range on the same arrays.
 `--only distance_transform`: the exact Euclidean distance transform (distance.hip) of 1024^3 uint8
 -> float32 on noise of density 0.5 and 0.999 and on a solid ball, at spacing (1, 1, 1) and
 (3, 1, 1), alternated with the Reencode uint8 -> float32 cast of the same volume (the streaming
@@ -910,6 +913,100 @@ def bench_connected_components(n, rounds=5, window_s=0.5, scipy_baseline=True, o
     return res
 
 
+def bench_label_statistics(n, rounds=5, window_s=0.5):
+    """Per-label statistics and the label size filter (labels.hip) on n^3 uint32 label arrays: the
+    three volumes of bench_connected_components labelled at connectivity 1 (K in the tens of
+    millions, mostly specks, and a few million blobs) and the dense one at connectivity 3 as well
+    (K = 1: every run lands on one label, the contention extreme). Per volume, alternated in one
+    run: Range on the label array (the yardstick: it reads the same bytes), the statistics'
+    device work (state init + accumulate with n_labels given) without and with a uint16
+    intensity array, and LabelSizeFilter (min_size 2) into uint32, which synchronises twice.
+    Windows of at least window_s after a warm-up, `rounds` of each, medians. "statistics" is device
+    work only; what a caller of LabelStatistics.apply_ndarray waits for (the range reduction for
+    n_labels, the kernels, the copy of the state to the host and the numpy columns) is timed once
+    per volume on the host clock as `apply_ndarray_s`."""
+    import math
+    import torch
+    import zarrs_tools_amd as zt
+    ctx = zt.default_context(0)
+    stream = torch.cuda.current_stream()
+    shape, total = (n, n, n), n ** 3
+    gen = torch.Generator(device="cuda").manual_seed(2025)
+    noise = torch.rand(shape, device="cuda", generator=gen)
+    u16 = zt.synth_u16(shape)
+    sample = u16.reshape(-1)[:: max(1, total // (1 << 20))].to(torch.float32)
+    level = float(torch.quantile(sample, 0.7))
+    masks = {"sparse_0.05_c1": ((noise < 0.05).to(torch.uint8), 1),
+             "dense_0.6_c1": ((noise < 0.6).to(torch.uint8), 1),
+             "dense_0.6_c3": ((noise < 0.6).to(torch.uint8), 3),
+             "blobs_c1": ((u16.to(torch.float32) > level).to(torch.uint8), 1)}
+    del noise, sample
+    labels, counts = {}, {}
+    for name, (m, c) in masks.items():
+        labels[name], counts[name] = zt.ConnectedComponents(c).apply_ndarray(m, "uint32", ctx=ctx)
+    ctx.release_scratch()
+    del masks
+    out = torch.empty(shape, dtype=torch.uint32, device="cuda")
+    rng, f = zt.Range(), zt.LabelStatistics()
+    rstate = rng.new_state("cuda", ctx)
+    size_filter = zt.LabelSizeFilter(min_size=2)
+    ops, kept = {}, {}
+    for name, lab in labels.items():
+        K = counts[name]
+        states = {False: f.new_state(3, K, False, "cuda", ctx),
+                  True: f.new_state(3, K, True, "cuda", ctx)}
+
+        def stats(lab=lab, K=K, inten=None, st=None):
+            zt._abi.check(zt.lib().zt_label_statistics_init(ctx.handle, 3, K, int(inten is not None),
+                                                            st.data_ptr()))
+            f.accumulate(lab, st, K, inten, None, ctx)
+
+        ops[f"{name}_range"] = (lambda lab=lab: rng.accumulate(lab, rstate, ctx))
+        ops[f"{name}_statistics"] = (lambda stats=stats, st=states[False]: stats(st=st))
+        ops[f"{name}_statistics_u16"] = (lambda stats=stats, st=states[True]:
+                                         stats(inten=u16, st=st))
+        kept[name] = size_filter.apply_ndarray(lab, "uint32", ctx, out=out)[1]
+        ops[f"{name}_size_filter"] = (lambda lab=lab: size_filter.apply_ndarray(lab, "uint32", ctx,
+                                                                               out=out))
+    reps = {}
+    for k, fn in ops.items():  # warm-up, then calls per window until it lasts window_s
+        r = 1
+        while True:
+            t = timed(fn, stream, r)
+            if t * r >= window_s * 1e3:
+                break
+            r = math.ceil(window_s * 1e3 / t * 1.05) + 1
+        reps[k] = r
+    ms = {k: [] for k in ops}
+    for _ in range(rounds):
+        for k, fn in ops.items():
+            ms[k].append(timed(fn, stream, reps[k]))
+    res = {"op": "label_statistics, label_size_filter on uint32 labels (device-resident)",
+           "config": {"shape": [n] * 3, "rounds": rounds, "window_s": window_s},
+           "n_labels": counts, "kept_min_size_2": kept, "ops": {}}
+    res["apply_ndarray_s"] = {}
+    for name, lab in labels.items():  # the whole call, host work included, once
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        got = zt.LabelStatistics().apply_ndarray(lab, ctx=ctx)
+        res["apply_ndarray_s"][name] = round(time.perf_counter() - t0, 3)
+        assert got["n_labels"] == counts[name]
+        del got
+    for k in ops:
+        v = sorted(ms[k])
+        med = v[len(v) // 2]
+        res["ops"][k] = {"ms": round(med, 4), "ms_min": round(v[0], 4), "ms_max": round(v[-1], 4),
+                         "spread": round((v[-1] - v[0]) / med, 4), "calls_per_window": reps[k],
+                         "ns_per_voxel": round(med * 1e6 / total, 5)}
+        if k.endswith("_range"):
+            gbs = total * 4 / (med / 1e3) / 1e9
+            res["ops"][k].update({"GB/s": round(gbs, 1), "hbm_frac": round(gbs / HBM_PEAK_GBS, 4)})
+        else:
+            base = k[:k.index("_c") + 3] + "_range"
+            res["ops"][k]["ratio_to_range"] = round(med / res["ops"][base]["ms"], 3)
+    return res
+
+
 def bench_distance_transform(n, rounds=5, window_s=0.5, scipy_baseline=True, once=False):
     """The exact Euclidean distance transform on n^3 uint8 device arrays -> float32
     (distance.hip) through DistanceTransform.apply, on noise of foreground density 0.5 (shallow
@@ -1167,6 +1264,8 @@ def main():
         print(json.dumps(bench_compare(a.gaussian_size)), flush=True)
     if "arithmetic" in only:  # with the float32 rescale yardstick, alternated
         print(json.dumps(bench_arithmetic(a.gaussian_size)), flush=True)
+    if "label_statistics" in only:  # with Range on the same label arrays, alternated
+        print(json.dumps(bench_label_statistics(a.gaussian_size)), flush=True)
     if "connected_components" in only:  # with the reencode uint8 -> uint32 yardstick, alternated
         print(json.dumps(bench_connected_components(
             a.gaussian_size, scipy_baseline=not a.no_scipy, once=a.cc_once)), flush=True)

@@ -28,6 +28,8 @@ from .filter import (  # noqa: E402
     GradientMagnitude,
     GuidedFilter,
     Histogram,
+    LabelSizeFilter,
+    LabelStatistics,
     Maximum,
     Median,
     Minimum,
@@ -40,9 +42,12 @@ from .filter import (  # noqa: E402
     SummedAreaTable,
     combine_compares,
     combine_histograms,
+    combine_label_statistics,
     combine_ranges,
     default_context,
     dtype_of,
+    label_size_filter,
+    label_statistics,
     pyramid,
     pyramid_level_shapes,
     synth_step_noise_f32,
@@ -67,4 +72,6 @@ __all__ = [
     "Arithmetic", "ARITHMETIC_OPERATORS",
     "ConnectedComponents",
     "DistanceTransform",
+    "LabelStatistics", "LabelSizeFilter", "combine_label_statistics", "label_statistics",
+    "label_size_filter",
 ]

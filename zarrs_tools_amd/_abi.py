@@ -85,6 +85,13 @@ AR_OPERATORS = {"add": 0, "subtract": 1, "multiply": 2, "divide": 3, "minimum": 
 CC_TILE = (8, 8, 64)
 
 
+# ZT_NO_DTYPE: the intensity type of a label statistics call without an intensity array;
+# ZT_LABELS_TILE_ROWS: the rows of a tile of its kernel (a tile is that many rows x 64 x)
+NO_DTYPE = -1
+LABELS_TILE_ROWS = 16
+LABELS_MAX = 2 ** 31 - 2
+
+
 def cc_tail_bytes(ndim: int) -> int:
     """The fixed part of the labelling's scratch: K and the offset table of a rank-ndim array."""
     return 64 + 16 * ((3 ** int(ndim) - 1) // 2)
@@ -246,6 +253,16 @@ def lib() -> ctypes.CDLL:
         "zt_distance_transform_memory": ([c_int, c_int, i64p, i64p, c_int, u64p], c_int),
         "zt_distance_transform_apply_array": ([vp, c_int, vp, c_int, vp, i64p, i64p, c_int,
                                                c_int], c_int),
+        "zt_label_statistics_is_compatible": ([c_int, c_int], c_int),
+        "zt_label_statistics_state_bytes": ([c_int, ctypes.c_int64, c_int, u64p], c_int),
+        "zt_label_statistics_init": ([vp, c_int, ctypes.c_int64, c_int, vp], c_int),
+        "zt_label_statistics_accumulate": ([vp, c_int, vp, c_int, vp, i64p, i64p, c_int,
+                                            ctypes.c_int64, vp], c_int),
+        "zt_label_statistics_finish": ([vp, vp, c_int, ctypes.c_int64, c_int, vp, u64p], c_int),
+        "zt_label_size_filter_is_compatible": ([c_int, c_int], c_int),
+        "zt_label_size_filter_memory": ([c_int, c_int, i64p, c_int, ctypes.c_int64, u64p], c_int),
+        "zt_label_size_filter_apply_array": ([vp, c_int, vp, c_int, vp, i64p, c_int,
+                                              ctypes.c_int64, ctypes.c_int64, c_int, u64p], c_int),
         "zt_range_is_compatible": ([c_int], c_int),
         "zt_histogram_is_compatible": ([c_int], c_int),
         "zt_range_init": ([vp, vp], c_int),

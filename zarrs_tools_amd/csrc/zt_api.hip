@@ -23,6 +23,7 @@
 #include "zt_device.hpp"
 #include "zt_edt_host.hpp"
 #include "zt_kernels.hpp"
+#include "zt_labels_host.hpp"
 
 namespace {
 
@@ -1741,6 +1742,268 @@ int zt_distance_transform_apply_array(zt_ctx* ctx, int dtype_in, const void* in,
                                   dtype_out, squared != 0, ctx->cur);
     if (e != hipSuccess) return hip_fail(e, "distance transform launch");
     if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev1, ctx->cur));
+    return ZT_OK;
+}
+
+// ---- per-label statistics and the label size filter (extensions; labels.hip) ---------------------
+
+static_assert(ZT_MAX_DIMS == zt::kLblMaxDims, "zt_labels_host.hpp and the public header agree");
+static_assert(ZT_LABELS_TILE_ROWS == zt::kLblTileRows, "the public header names the tile");
+
+namespace {
+
+int lbl_fail(int status, int64_t n_labels) {
+    switch (status) {
+    case zt::kLblOk: return ZT_OK;
+    case zt::kLblBadLabels:
+        return fail(ZT_ERR_INVALID_PARAMETERS, "label_statistics: n_labels %lld not in [0, %lld]",
+                    (long long)n_labels, (long long)zt::kLblMaxLabels);
+    case zt::kLblBadOrigin:
+        return fail(ZT_ERR_INVALID_PARAMETERS,
+                    "label_statistics: every origin must be >= 0 and origin + extent an int64");
+    case zt::kLblTooManyElems:
+        return fail(ZT_ERR_INVALID_PARAMETERS,
+                    "label_statistics: the box has more than %lld elements",
+                    (long long)zt::kLblMaxElems);
+    case zt::kLblSumWraps:
+        return fail(ZT_ERR_INVALID_PARAMETERS,
+                    "label_statistics: elements * (origin + extent) must be below 2^64, so that "
+                    "no coordinate sum wraps");
+    default:
+        return fail(ZT_ERR_INVALID_PARAMETERS, "label_statistics: the state is too large");
+    }
+}
+
+int lbl_state_ok(const void* state) {
+    if (!state || ((uintptr_t)state % 8) != 0)
+        return fail(ZT_ERR_INVALID_PARAMETERS,
+                    "the label statistics state is device memory, 8-byte aligned");
+    return ZT_OK;
+}
+
+int lbl_ndim_ok(int ndim) {
+    if (ndim < 1 || ndim > ZT_MAX_DIMS)
+        return fail(ZT_ERR_INVALID_PARAMETERS, "label_statistics: ndim %d not in [1, %d]", ndim,
+                    ZT_MAX_DIMS);
+    return ZT_OK;
+}
+
+}  // namespace
+
+int zt_label_statistics_is_compatible(int dtype_labels, int dtype_intensity) {
+    if (!valid_dtype(dtype_labels))
+        return fail(ZT_ERR_UNSUPPORTED_DATA_TYPE, "Unsupported data type code %d", dtype_labels);
+    if (cc_label_max(dtype_labels) == 0)
+        return fail(ZT_ERR_UNSUPPORTED_DATA_TYPE,
+                    "label_statistics: labels need an integer type, not %s",
+                    dtype_name(dtype_labels));
+    if (dtype_intensity == ZT_NO_DTYPE) return ZT_OK;
+    if (!valid_dtype(dtype_intensity))
+        return fail(ZT_ERR_UNSUPPORTED_DATA_TYPE, "Unsupported data type code %d",
+                    dtype_intensity);
+    if (dtype_intensity == ZT_BOOL)
+        return fail(ZT_ERR_UNSUPPORTED_DATA_TYPE,
+                    "label_statistics: intensities need a numeric type, not bool");
+    return ZT_OK;
+}
+
+int zt_label_statistics_state_bytes(int ndim, int64_t n_labels, int with_intensity,
+                                    uint64_t* bytes) {
+    if (int rc = lbl_ndim_ok(ndim)) return rc;
+    if (!bytes) return fail(ZT_ERR_INVALID_PARAMETERS, "null pointer");
+    zt::LblPlan plan;
+    if (int rc = lbl_fail(zt::lbl_state(ndim, n_labels, with_intensity != 0, false, &plan),
+                          n_labels))
+        return rc;
+    *bytes = plan.state_bytes;
+    return ZT_OK;
+}
+
+int zt_label_statistics_init(zt_ctx* ctx, int ndim, int64_t n_labels, int with_intensity,
+                             void* state) {
+    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = lbl_ndim_ok(ndim)) return rc;
+    zt::LblPlan plan;
+    if (int rc = lbl_fail(zt::lbl_state(ndim, n_labels, with_intensity != 0, false, &plan),
+                          n_labels))
+        return rc;
+    if (int rc = lbl_state_ok(state)) return rc;
+    DeviceGuard guard(ctx->device);
+    hipError_t e = zt::launch_lbl_init(state, ndim, n_labels, with_intensity != 0, false, ctx->cur);
+    if (e != hipSuccess) return hip_fail(e, "label statistics init launch");
+    return ZT_OK;
+}
+
+int zt_label_statistics_accumulate(zt_ctx* ctx, int dtype_labels, const void* labels,
+                                   int dtype_intensity, const void* intensity,
+                                   const int64_t* box_shape, const int64_t* origin, int ndim,
+                                   int64_t n_labels, void* state) {
+    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = zt_label_statistics_is_compatible(dtype_labels, dtype_intensity)) return rc;
+    if (int rc = check_shape(box_shape, ndim, "box_shape")) return rc;
+    if ((dtype_intensity == ZT_NO_DTYPE) != (intensity == nullptr))
+        return fail(ZT_ERR_INVALID_PARAMETERS,
+                    "label_statistics: an intensity array and its data type go together");
+    zt::LblPlan plan;
+    if (int rc = lbl_fail(zt::lbl_plan(box_shape, origin, ndim, n_labels, intensity != nullptr,
+                                       false, &plan),
+                          n_labels))
+        return rc;
+    if (int rc = lbl_state_ok(state)) return rc;
+    if (plan.n == 0) return ZT_OK;
+    if (!labels) return fail(ZT_ERR_INVALID_PARAMETERS, "null data pointer");
+    if (((uintptr_t)labels % zt::dtype_size(dtype_labels)) != 0 ||
+        (intensity && ((uintptr_t)intensity % zt::dtype_size(dtype_intensity)) != 0))
+        return fail(ZT_ERR_INVALID_PARAMETERS, "data pointers must be element aligned");
+    DeviceGuard guard(ctx->device);
+    if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev0, ctx->cur));
+    hipError_t e = zt::launch_lbl_accumulate(labels, dtype_labels, intensity, dtype_intensity,
+                                             box_shape, origin, ndim, n_labels, false, state,
+                                             ctx->cur);
+    if (e != hipSuccess) return hip_fail(e, "label statistics launch");
+    if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev1, ctx->cur));
+    return ZT_OK;
+}
+
+int zt_label_statistics_finish(zt_ctx* ctx, const void* state, int ndim, int64_t n_labels,
+                               int with_intensity, uint64_t* host_state, uint64_t* invalid) {
+    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = lbl_ndim_ok(ndim)) return rc;
+    zt::LblPlan plan;
+    if (int rc = lbl_fail(zt::lbl_state(ndim, n_labels, with_intensity != 0, false, &plan),
+                          n_labels))
+        return rc;
+    if (int rc = lbl_state_ok(state)) return rc;
+    DeviceGuard guard(ctx->device);
+    uint64_t bad = 0;
+    const uint64_t* words = static_cast<const uint64_t*>(state);
+    if (host_state)
+        ZT_HIP(hipMemcpyAsync(host_state, state, (size_t)plan.state_bytes, hipMemcpyDeviceToHost,
+                              ctx->cur));
+    ZT_HIP(hipMemcpyAsync(&bad, words + plan.state_words - 1, sizeof bad, hipMemcpyDeviceToHost,
+                          ctx->cur));
+    ZT_HIP(hipStreamSynchronize(ctx->cur));
+    if (invalid) *invalid = bad;
+    if (bad)
+        return fail(ZT_ERR_INVALID_PARAMETERS, "label_statistics: %llu elements outside [0, %lld]",
+                    (unsigned long long)bad, (long long)n_labels);
+    return ZT_OK;
+}
+
+int zt_label_size_filter_is_compatible(int dtype_in, int dtype_out) {
+    for (int d : {dtype_in, dtype_out}) {
+        if (!valid_dtype(d))
+            return fail(ZT_ERR_UNSUPPORTED_DATA_TYPE, "Unsupported data type code %d", d);
+        if (cc_label_max(d) == 0)
+            return fail(ZT_ERR_UNSUPPORTED_DATA_TYPE,
+                        "label_size_filter: labels need an integer type, not %s", dtype_name(d));
+    }
+    return ZT_OK;
+}
+
+namespace {
+
+int lsf_sizes_ok(int64_t min_size, int64_t max_size) {
+    if (min_size < 1)
+        return fail(ZT_ERR_INVALID_PARAMETERS, "label_size_filter: min_size %lld is below 1",
+                    (long long)min_size);
+    if (max_size >= 0 && max_size < min_size)
+        return fail(ZT_ERR_INVALID_PARAMETERS,
+                    "label_size_filter: max_size %lld is below min_size %lld", (long long)max_size,
+                    (long long)min_size);
+    return ZT_OK;
+}
+
+int lsf_elems(const int64_t* shape, int ndim, int64_t* n) {
+    if (int rc = check_shape(shape, ndim, "shape")) return rc;
+    zt::LblPlan plan;
+    if (int rc = lbl_fail(zt::lbl_plan(shape, nullptr, ndim, 0, false, true, &plan), 0)) return rc;
+    *n = plan.n;
+    return ZT_OK;
+}
+
+}  // namespace
+
+int zt_label_size_filter_memory(int dtype_in, int dtype_out, const int64_t* shape, int ndim,
+                                int64_t n_labels, uint64_t* bytes) {
+    if (int rc = zt_label_size_filter_is_compatible(dtype_in, dtype_out)) return rc;
+    int64_t n = 0;
+    if (int rc = lsf_elems(shape, ndim, &n)) return rc;
+    if (!bytes) return fail(ZT_ERR_INVALID_PARAMETERS, "null pointer");
+    uint64_t scratch = 0;
+    if (int rc = lbl_fail(zt::lbl_filter_scratch(n_labels, &scratch), n_labels)) return rc;
+    *bytes = n == 0 ? 0
+                    : (uint64_t)n * (zt::dtype_size(dtype_in) + zt::dtype_size(dtype_out)) + scratch;
+    return ZT_OK;
+}
+
+int zt_label_size_filter_apply_array(zt_ctx* ctx, int dtype_in, const void* in, int dtype_out,
+                                     void* out, const int64_t* shape, int ndim, int64_t min_size,
+                                     int64_t max_size, int relabel, uint64_t* kept) {
+    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = zt_label_size_filter_is_compatible(dtype_in, dtype_out)) return rc;
+    if (int rc = lsf_sizes_ok(min_size, max_size)) return rc;
+    int64_t n = 0;
+    if (int rc = lsf_elems(shape, ndim, &n)) return rc;
+    if (kept) *kept = 0;
+    if (n == 0) return ZT_OK;
+    if (!in || !out) return fail(ZT_ERR_INVALID_PARAMETERS, "null data pointer");
+    const uintptr_t a0 = (uintptr_t)in, a1 = a0 + (size_t)n * zt::dtype_size(dtype_in);
+    const uintptr_t b0 = (uintptr_t)out, b1 = b0 + (size_t)n * zt::dtype_size(dtype_out);
+    if (a0 < b1 && b0 < a1)
+        return fail(ZT_ERR_INVALID_PARAMETERS, "input and output must not overlap");
+    if ((a0 % zt::dtype_size(dtype_in)) != 0 || (b0 % zt::dtype_size(dtype_out)) != 0)
+        return fail(ZT_ERR_INVALID_PARAMETERS, "data pointers must be element aligned");
+    DeviceGuard guard(ctx->device);
+    // 1. the largest label (and the smallest: a negative element is refused here)
+    if (int rc = ctx->ensure_scratch(16)) return rc;
+    if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev0, ctx->cur));
+    hipError_t e = zt::launch_range_init(ctx->scratch, ctx->cur);
+    if (e == hipSuccess) e = zt::launch_range_accumulate(in, dtype_in, n, ctx->scratch, ctx->cur);
+    if (e != hipSuccess) return hip_fail(e, "label size filter range launch");
+    uint64_t keys[2] = {0, 0}, lo = 0, hi = 0;
+    ZT_HIP(hipMemcpyAsync(keys, ctx->scratch, sizeof keys, hipMemcpyDeviceToHost, ctx->cur));
+    ZT_HIP(hipStreamSynchronize(ctx->cur));
+    zt::range_decode(dtype_in, keys[0], &lo);
+    zt::range_decode(dtype_in, keys[1], &hi);
+    const int bits = 8 * (int)zt::dtype_size(dtype_in);
+    if (dtype_in <= ZT_INT64 && ((lo >> (bits - 1)) & 1))
+        return fail(ZT_ERR_INVALID_PARAMETERS, "label_size_filter: the labels have a negative element");
+    if (hi > (uint64_t)zt::kLblMaxLabels)
+        return fail(ZT_ERR_INVALID_PARAMETERS,
+                    "label_size_filter: the largest label %llu is above %lld",
+                    (unsigned long long)hi, (long long)zt::kLblMaxLabels);
+    const int64_t K = (int64_t)hi;
+    // 2. counts, 3. keep and scan
+    uint64_t scratch_bytes = 0;
+    if (int rc = lbl_fail(zt::lbl_filter_scratch(K, &scratch_bytes), K)) return rc;
+    if (int rc = ctx->ensure_scratch((size_t)scratch_bytes)) return rc;
+    uint8_t* base = static_cast<uint8_t*>(ctx->scratch);
+    void* counts = base;
+    void* remap = base + 8 * ((size_t)K + 2);
+    void* tail = base + scratch_bytes - 16;
+    e = zt::launch_lbl_init(counts, 1, K, false, true, ctx->cur);
+    if (e == hipSuccess)
+        e = zt::launch_lbl_accumulate(in, dtype_in, nullptr, ZT_NO_DTYPE, shape, nullptr, ndim, K,
+                                      true, counts, ctx->cur);
+    if (e == hipSuccess)
+        e = zt::launch_lbl_keep_scan(counts, K, (uint64_t)min_size,
+                                     max_size < 0 ? ~0ull : (uint64_t)max_size, relabel != 0, remap,
+                                     tail, ctx->cur);
+    if (e != hipSuccess) return hip_fail(e, "label size filter launch");
+    // K' and the largest label kept come back before anything is written: labels never wrap
+    uint64_t res[2] = {0, 0};
+    ZT_HIP(hipMemcpyAsync(res, tail, sizeof res, hipMemcpyDeviceToHost, ctx->cur));
+    ZT_HIP(hipStreamSynchronize(ctx->cur));
+    const uint64_t largest = relabel ? res[0] : res[1];
+    if (largest > cc_label_max(dtype_out))
+        return fail(ZT_ERR_INVALID_PARAMETERS, "label_size_filter: the largest label %llu does not fit %s",
+                    (unsigned long long)largest, dtype_name(dtype_out));
+    // 4. out[i] = remap[in[i]]
+    e = zt::launch_lbl_gather(in, dtype_in, remap, out, dtype_out, n, ctx->cur);
+    if (e != hipSuccess) return hip_fail(e, "label size filter write launch");
+    if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev1, ctx->cur));
+    if (kept) *kept = res[0];
     return ZT_OK;
 }
 

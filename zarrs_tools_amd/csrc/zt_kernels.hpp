@@ -289,6 +289,35 @@ hipError_t launch_edt(const void* in, int dtype_in, const int64_t* shape, int nd
                       const uint64_t* weight, bool work64, void* scratch, void* out, int dtype_out,
                       int squared, hipStream_t s);
 
+// Per-label statistics and the label size filter (labels.hip; extensions, no reference operation;
+// DESIGN.md §3.15). The state's layout, size and limits are zt_labels_host.hpp's. A workgroup of
+// the statistics owns tiles of kLblTileRows rows x 64 x of the box and an LDS table of at most
+// kLblSlots labels (lbl_slots: fewer when the columns of a rank need it, or ZT_LABELS_LDS_SLOTS);
+// the grid is capped at lbl_max_blocks() (ZT_LABELS_MAX_BLOCKS lowers it) and loops.
+// launch_lbl_accumulate folds the contiguous C-order box `shape` at `origin` (NULL = zeros) of the
+// whole array into `state`; intensity == NULL: no intensity columns; count_only: the count column
+// alone. launch_lbl_keep_scan turns a count-only state into remap[0 .. K] (uint32_t: 0 for a label
+// whose count is outside [min_size, max_size], else its rank among the kept ones + 1, or itself
+// without `relabel`) and kept[0] = the kept count, kept[1] = the largest label kept;
+// launch_lbl_gather writes out[i] = remap[in[i]] (every in[i] in [0, K]). Everything runs on `s`;
+// nothing synchronises.
+constexpr int kLblTileRows = 16;
+constexpr int kLblSlots = 256;
+int lbl_max_blocks();
+int lbl_slots(int cols);
+bool lbl_intensity_sums(int dtype);  // the six integer types of up to 32 bits
+hipError_t launch_lbl_init(void* state, int ndim, int64_t n_labels, bool intensity,
+                           bool count_only, hipStream_t s);
+hipError_t launch_lbl_accumulate(const void* labels, int dtype_labels, const void* intensity,
+                                 int dtype_intensity, const int64_t* shape, const int64_t* origin,
+                                 int ndim, int64_t n_labels, bool count_only, void* state,
+                                 hipStream_t s);
+hipError_t launch_lbl_keep_scan(const void* count_state, int64_t n_labels, uint64_t min_size,
+                                uint64_t max_size, bool relabel, void* remap, void* kept,
+                                hipStream_t s);
+hipError_t launch_lbl_gather(const void* in, int dtype_in, const void* remap, void* out,
+                             int dtype_out, int64_t n, hipStream_t s);
+
 // zarrs_info reductions (info.hip; src/info/range.rs, src/info/histogram.rs) over a contiguous
 // run of n elements of `dtype` (the 12 numeric types) at element alignment.
 // Range: `state` is two device u64 words (smallest key, largest key) that accumulate across

@@ -27,6 +27,10 @@ Names, argument meaning and error behaviour follow LDeakin/zarrs_tools 0.7.2:
     connected sets of non-zero elements); its semantics are DESIGN.md §3.13
   - ``DistanceTransform``: an extension with no counterpart in the reference (the exact Euclidean
     distance to the nearest zero element); its semantics are DESIGN.md §3.14
+  - ``LabelStatistics``, ``LabelSizeFilter``: extensions with no counterpart in the reference
+    (per-label count, bounding box, centroid and intensity statistics of a label array, and the
+    removal of labels by size; ``combine_label_statistics`` joins partial results); their
+    semantics are DESIGN.md §3.15
   - ``chunk_occupancy`` <- zarrs' ``store_empty_chunks = false`` (which chunks of a device
     array hold anything but the fill value)
   - ``ArraySubsetOverlap`` <- src/filter/array_subset_overlap.rs:4-52
@@ -1476,6 +1480,357 @@ class DistanceTransform:
         """The filter's `apply` over device-resident arrays."""
         x, dtype_in = _info_run(input)
         self._run(x, dtype_in, output.data, output.dtype, ctx)
+
+
+_LABEL_TYPES = ("int8", "int16", "int32", "int64", "uint8", "uint16", "uint32", "uint64")
+# intensity types whose sums are kept (exact integers); the 64-bit and float types give None
+LABEL_SUM_TYPES = ("int8", "int16", "int32", "uint8", "uint16", "uint32")
+
+
+def _exact_quotient(num, den):
+    """num / den per element as the correctly rounded f64 quotient of the two integers (Python's
+    int / int); NaN where den == 0. num: an object array of Python ints, den: uint64."""
+    import numpy as np
+    out = np.full(num.shape, np.nan, dtype=np.float64)
+    d = np.broadcast_to(den.reshape(den.shape + (1,) * (num.ndim - den.ndim)), num.shape)
+    for i in np.ndindex(num.shape):
+        if d[i]:
+            out[i] = int(num[i]) / int(d[i])
+    return out
+
+
+def _quotient(num, den):
+    """_exact_quotient, vectorised where both integers are below 2^53 in magnitude (f64 holds
+    them, and IEEE division rounds correctly); the Python loop only for the entries beyond."""
+    import numpy as np
+    d = np.broadcast_to(den.reshape(den.shape + (1,) * (num.ndim - den.ndim)), num.shape)
+    if num.size == 0:
+        return np.full(num.shape, np.nan, dtype=np.float64)
+    f = num.astype(np.float64)  # exact below 2^53; the entries beyond are redone as integers
+    small = (np.abs(f) < 2.0 ** 53) & (d < np.uint64(2 ** 53))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out = np.where(d != 0, f / d.astype(np.float64), np.nan)
+    rest = ~small & (d != 0)
+    if rest.any():
+        obj = num.astype(object)
+        for i in zip(*np.nonzero(rest)):
+            out[i] = int(obj[i]) / int(d[i])
+    return out
+
+
+def _sums_128(lo, hi):
+    """The 128-bit two's complement sums (lo, hi: uint64 columns) as an object array of Python
+    ints: one vectorised step where the sum fits an int64 (hi is the sign extension of lo), a loop
+    over the others."""
+    import numpy as np
+    neg = lo >= np.uint64(1 << 63)
+    fits = np.where(neg, hi == np.uint64(2 ** 64 - 1), hi == np.uint64(0))
+    sums = lo.view(np.int64).astype(object)
+    for i in np.flatnonzero(~fits):
+        v = (int(hi[i]) << 64) | int(lo[i])
+        sums[i] = v - (1 << 128) if v >> 127 else v
+    return sums
+
+
+def _keys_to_values(keys, dtype: str):
+    """The elements whose orderable keys (include/zarrs_tools_amd.h) are `keys` (uint64), as a
+    numpy array of `dtype` (bfloat16 widened exactly to float32)."""
+    import numpy as np
+    nbits = 8 * {"bfloat16": 2, "float16": 2, "float32": 4, "float64": 8}.get(
+        dtype, _INT_BITS.get(dtype, 0) // 8)
+    u = np.dtype(f"uint{nbits}")
+    sign = np.uint64(1 << (nbits - 1))
+    mask = np.uint64((1 << nbits) - 1)
+    if dtype.startswith("uint"):
+        return keys.astype(u)
+    if dtype.startswith("int"):
+        return (keys ^ sign).astype(u).view(np.dtype(f"int{nbits}"))
+    bits = np.where((keys & sign) != 0, keys & ~sign, ~keys & mask).astype(u)
+    if dtype == "bfloat16":
+        return (bits.astype(np.uint32) << np.uint32(16)).view(np.float32)
+    return bits.view(np.dtype(f"float{nbits}"))
+
+
+def _label_result(K, ndim, count, cmin, cmax, csum, total, intensity=None):
+    """The result dict from the columns of labels 1 .. K. intensity: (dtype, valid, min, max,
+    sums or None)."""
+    import numpy as np
+    present = count != 0
+    res = {
+        "n_labels": int(K),
+        "background": int(total) - int(count.sum(dtype=np.uint64)),
+        "count": count,
+        "bbox_min": np.where(present[:, None], cmin.astype(np.int64), -1),
+        "bbox_max": np.where(present[:, None], cmax.astype(np.int64), -1),
+        "coord_sum": csum,
+        "centroid": _quotient(csum, count),
+    }
+    if intensity is not None:
+        dtype, valid, imin, imax, sums = intensity
+        res["intensity_dtype"] = dtype
+        res["intensity_valid"] = valid
+        res["intensity_min"] = imin
+        res["intensity_max"] = imax
+        res["intensity_sum"] = sums
+        res["intensity_mean"] = None if sums is None else _quotient(sums, count)
+    return res
+
+
+def combine_label_statistics(parts):
+    """The statistics of the union of disjoint boxes that each gave a LabelStatistics result for
+    the same n_labels (and intensity type): counts and sums add, minima and maxima fold."""
+    import numpy as np
+    parts = list(parts)
+    if not parts:
+        raise _invalid("combine_label_statistics: no parts")
+    K, nd = parts[0]["n_labels"], parts[0]["bbox_min"].shape[1]
+    with_i = "intensity_min" in parts[0]
+    for p in parts:
+        if p["n_labels"] != K or p["bbox_min"].shape[1] != nd or ("intensity_min" in p) != with_i \
+                or (with_i and p["intensity_dtype"] != parts[0]["intensity_dtype"]):
+            raise _invalid("combine_label_statistics: the parts differ in n_labels, rank or "
+                           "intensity type")
+    count = np.zeros(K, dtype=np.uint64)
+    csum = np.zeros((K, nd), dtype=np.uint64)
+    cmin = np.full((K, nd), np.iinfo(np.int64).max, dtype=np.int64)
+    cmax = np.full((K, nd), -1, dtype=np.int64)
+    total = 0
+    for p in parts:
+        here = (p["count"] != 0)[:, None]
+        count += p["count"]
+        csum += p["coord_sum"]
+        cmin = np.where(here, np.minimum(cmin, p["bbox_min"]), cmin)
+        cmax = np.where(here, np.maximum(cmax, p["bbox_max"]), cmax)
+        total += p["background"] + int(p["count"].sum(dtype=np.uint64))
+    intensity = None
+    if with_i:
+        first = parts[0]
+        valid = first["intensity_valid"].copy()
+        imin, imax = first["intensity_min"].copy(), first["intensity_max"].copy()
+        sums = None if first["intensity_sum"] is None else first["intensity_sum"].copy()
+        for p in parts[1:]:
+            v, a, b = p["intensity_valid"], p["intensity_min"], p["intensity_max"]
+            # -0.0 orders below +0.0, as the kernels' keys do
+            lower = (a < imin) | ((a == imin) & np.signbit(a) & ~np.signbit(imin))
+            upper = (b > imax) | ((b == imax) & ~np.signbit(b) & np.signbit(imax))
+            imin = np.where(v & (~valid | lower), a, imin)
+            imax = np.where(v & (~valid | upper), b, imax)
+            valid = valid | v
+            if sums is not None:
+                sums = sums + p["intensity_sum"]
+        intensity = (first["intensity_dtype"], valid, imin, imax, sums)
+    return _label_result(K, nd, count, cmin, cmax, csum, total, intensity)
+
+
+class LabelStatistics:
+    """An extension with no counterpart in the reference: per label 1 .. K of an
+    integer label array (0 = background) the element count, the bounding box (inclusive), the
+    coordinate sums and the centroid, and with an intensity array of the same shape the smallest,
+    largest, summed and mean intensity. Every result is exact: counts, sums, minima and maxima are
+    integers reduced on the device, the centroid and the mean are the correctly rounded f64
+    quotients of two integers. n_labels=None takes the largest label present. A label element
+    below 0 or above n_labels raises InvalidParameters."""
+
+    def __init__(self, n_labels: Optional[int] = None):
+        self.n_labels = None if n_labels is None else int(n_labels)
+        if self.n_labels is not None and not 0 <= self.n_labels <= _abi.LABELS_MAX:
+            raise _invalid(f"label_statistics: n_labels {self.n_labels} not in "
+                           f"[0, {_abi.LABELS_MAX}]")
+
+    def name(self) -> str:
+        return "label statistics"
+
+    def is_compatible(self, dtype_labels: str, dtype_intensity: Optional[str] = None) -> None:
+        check(lib().zt_label_statistics_is_compatible(
+            _info_dtype(dtype_labels),
+            _abi.NO_DTYPE if dtype_intensity is None else _info_dtype(dtype_intensity)))
+
+    def state_bytes(self, ndim: int, n_labels: Optional[int] = None,
+                    with_intensity: bool = False) -> int:
+        """Bytes of the device state of `n_labels` labels (default: the filter's) over ndim axes."""
+        K = self.n_labels if n_labels is None else int(n_labels)
+        if K is None:
+            raise _invalid("label_statistics: state_bytes needs n_labels")
+        out = ctypes.c_uint64()
+        check(lib().zt_label_statistics_state_bytes(int(ndim), K, int(bool(with_intensity)),
+                                                    ctypes.byref(out)))
+        return int(out.value)
+
+    def largest_label(self, labels, ctx: Optional[Context] = None) -> int:
+        """The n_labels that n_labels=None stands for: the largest element, at least 0."""
+        lo, hi = Range().apply_ndarray(labels, ctx)
+        return max(0, int(hi)) if hi is not None else 0
+
+    def new_state(self, ndim: int, n_labels: int, with_intensity: bool, device=None,
+                  ctx: Optional[Context] = None):
+        """An empty device state that `accumulate` folds boxes into."""
+        torch = _torch()
+        words = self.state_bytes(ndim, n_labels, with_intensity) // 8
+        state = torch.empty(words, dtype=torch.int64, device="cuda" if device is None else device)
+        ctx = ctx or default_context(state.device.index)
+        check(lib().zt_label_statistics_init(ctx.handle, int(ndim), int(n_labels),
+                                             int(bool(with_intensity)), _ptr(state)))
+        return state
+
+    def accumulate(self, labels, state, n_labels: int, intensity=None, origin=None,
+                   ctx: Optional[Context] = None) -> None:
+        """Folds the box `labels` (with `intensity`) that lies at `origin` of the whole array."""
+        x, dtype_l = _info_run(labels)
+        y, dtype_i = _info_run(intensity) if intensity is not None else (None, None)
+        self.is_compatible(dtype_l, dtype_i)
+        if y is not None and tuple(y.shape) != tuple(x.shape):
+            raise _invalid(f"Array shapes do not match: {list(x.shape)} vs {list(y.shape)}")
+        if y is not None and y.device != x.device:
+            raise _invalid("label_statistics: the arrays are on different devices")
+        if origin is not None and len(origin) != x.dim():
+            raise _invalid("label_statistics: origin must have one entry per axis")
+        ctx = ctx or default_context(x.device.index)
+        check(lib().zt_label_statistics_accumulate(
+            ctx.handle, DTYPES[dtype_l], _ptr(x),
+            _abi.NO_DTYPE if y is None else DTYPES[dtype_i], None if y is None else _ptr(y),
+            i64_array(x.shape), None if origin is None else i64_array(origin), x.dim(),
+            int(n_labels), _ptr(state)))
+
+    def finish(self, state, ndim: int, n_labels: int, total: int,
+               dtype_intensity: Optional[str] = None, ctx: Optional[Context] = None) -> dict:
+        """The result dict of everything folded into `state`; `total` is the number of elements
+        folded (background = total - the sum of the counts). Arrays are indexed by label - 1."""
+        import numpy as np
+        K, nd, with_i = int(n_labels), int(ndim), dtype_intensity is not None
+        ctx = ctx or default_context(state.device.index)
+        host = np.empty(self.state_bytes(nd, K, with_i) // 8, dtype=np.uint64)
+        bad = ctypes.c_uint64()
+        check(lib().zt_label_statistics_finish(
+            ctx.handle, _ptr(state), nd, K, int(with_i), ctypes.c_void_p(host.ctypes.data),
+            ctypes.byref(bad)))
+        cols = host[:-1].reshape(-1, K + 1)[:, 1:]
+        count = cols[0].copy()
+        cmin = np.stack([cols[1 + 3 * a] for a in range(nd)], axis=1)
+        cmax = np.stack([cols[2 + 3 * a] for a in range(nd)], axis=1)
+        csum = np.stack([cols[3 + 3 * a] for a in range(nd)], axis=1)
+        intensity = None
+        if with_i:
+            klo, khi = cols[1 + 3 * nd], cols[2 + 3 * nd]
+            valid = klo <= khi
+            imin = _keys_to_values(np.where(valid, klo, khi), dtype_intensity)
+            imax = _keys_to_values(khi, dtype_intensity)
+            if imin.dtype.kind == "f":
+                imin = np.where(valid, imin, np.nan).astype(imin.dtype)
+                imax = np.where(valid, imax, np.nan).astype(imax.dtype)
+            else:
+                imin = np.where(valid, imin, 0).astype(imin.dtype)
+                imax = np.where(valid, imax, 0).astype(imax.dtype)
+            sums = None
+            if dtype_intensity in LABEL_SUM_TYPES:
+                sums = _sums_128(cols[3 + 3 * nd], cols[4 + 3 * nd])
+            intensity = (dtype_intensity, valid, imin, imax, sums)
+        return _label_result(K, nd, count, cmin, cmax, csum, total, intensity)
+
+    def apply_ndarray(self, labels, intensity=None, ctx: Optional[Context] = None) -> dict:
+        """The statistics of a device tensor of labels (and one of intensities) as a dict of numpy
+        arrays indexed by label - 1: count (uint64), bbox_min / bbox_max (int64, K x ndim, -1 for
+        an absent label), coord_sum (uint64), centroid (float64, NaN for an absent label), and
+        n_labels, background as ints; with intensity also intensity_valid, intensity_min,
+        intensity_max (the intensity type; bfloat16 as float32), intensity_sum (Python ints) and
+        intensity_mean (float64), the last two None for the 64-bit and float types."""
+        x, dtype_l = _info_run(labels)
+        y, dtype_i = _info_run(intensity) if intensity is not None else (None, None)
+        self.is_compatible(dtype_l, dtype_i)
+        if y is not None and tuple(y.shape) != tuple(x.shape):
+            raise _invalid(f"Array shapes do not match: {list(x.shape)} vs {list(y.shape)}")
+        ctx = ctx or default_context(x.device.index)
+        K = self.n_labels if self.n_labels is not None else self.largest_label(x, ctx)
+        if K > _abi.LABELS_MAX:
+            raise _invalid(f"label_statistics: n_labels {K} not in [0, {_abi.LABELS_MAX}]")
+        nd = max(x.dim(), 1)
+        if x.dim() == 0:
+            raise _invalid("label_statistics: ndim 0 not in [1, 8]")
+        state = self.new_state(nd, K, y is not None, x.device, ctx)
+        self.accumulate(x, state, K, y, None, ctx)
+        return self.finish(state, nd, K, x.numel(), dtype_i, ctx)
+
+
+def label_statistics(labels, n_labels: Optional[int] = None, intensity=None,
+                     ctx: Optional[Context] = None) -> dict:
+    """LabelStatistics(n_labels).apply_ndarray(labels, intensity)."""
+    return LabelStatistics(n_labels).apply_ndarray(labels, intensity, ctx)
+
+
+class LabelSizeFilter:
+    """An extension with no counterpart in the reference: a label whose element
+    count lies in [min_size, max_size] is kept, every other label becomes 0. With `relabel` the
+    kept labels are renumbered 1 .. K' in increasing order of their old value; otherwise they keep
+    their values. The eight integer types in and out (the input type by default). A whole-array
+    operation: a label may span every chunk."""
+
+    def __init__(self, min_size: int = 1, max_size: Optional[int] = None, relabel: bool = True):
+        self.min_size = int(min_size)
+        self.max_size = None if max_size is None else int(max_size)
+        self.relabel = bool(relabel)
+        if self.min_size < 1:
+            raise _invalid(f"label_size_filter: min_size {self.min_size} is below 1")
+        if self.max_size is not None and self.max_size < self.min_size:
+            raise _invalid(f"label_size_filter: max_size {self.max_size} is below min_size "
+                           f"{self.min_size}")
+
+    def name(self) -> str:
+        return "label size filter"
+
+    def is_compatible(self, dtype_in: str, dtype_out: str) -> None:
+        check(lib().zt_label_size_filter_is_compatible(_info_dtype(dtype_in),
+                                                       _info_dtype(dtype_out)))
+
+    def memory(self, dtype_in: str, dtype_out: str, shape, n_labels: int) -> int:
+        """Device bytes of one call on an array of `shape` whose largest label is n_labels:
+        input + scratch + output."""
+        out = ctypes.c_uint64()
+        check(lib().zt_label_size_filter_memory(
+            _info_dtype(dtype_in), _info_dtype(dtype_out), i64_array(shape), len(shape),
+            int(n_labels), ctypes.byref(out)))
+        return int(out.value)
+
+    def _run(self, x, dtype_in, out, dtype_out, ctx) -> int:
+        if tuple(out.shape) != tuple(x.shape):
+            raise _invalid(f"Array shapes do not match: {list(x.shape)} vs {list(out.shape)}")
+        if x.device != out.device:
+            raise _invalid("label_size_filter: the arrays are on different devices")
+        if not out.is_contiguous():
+            raise _invalid("label_size_filter: the output must be contiguous")
+        self.is_compatible(dtype_in, dtype_out)
+        ctx = ctx or default_context(x.device.index)
+        kept = ctypes.c_uint64()
+        check(lib().zt_label_size_filter_apply_array(
+            ctx.handle, DTYPES[dtype_in], _ptr(x), DTYPES[dtype_out], _ptr(out),
+            i64_array(x.shape), x.dim(), self.min_size,
+            -1 if self.max_size is None else self.max_size, int(self.relabel),
+            ctypes.byref(kept)))
+        return int(kept.value)
+
+    def apply_ndarray(self, v, dtype_out: Optional[str] = None, ctx: Optional[Context] = None,
+                      out=None):
+        """Filters a device tensor of labels; returns (out, K'). out is a new tensor of
+        `dtype_out` (default: the input type), or `out` (contiguous, not overlapping the input).
+        When the largest output label does not fit `dtype_out` the call raises InvalidParameters
+        and writes nothing."""
+        x, dtype_in = _info_run(v)
+        dtype_out = dtype_out or (dtype_of(out) if out is not None else dtype_in)
+        if out is None:
+            self.is_compatible(dtype_in, dtype_out)
+            out = _torch().empty(tuple(x.shape), dtype=torch_dtype(dtype_out), device=x.device)
+        return out, self._run(x, dtype_in, out, dtype_out, ctx)
+
+    def apply(self, input: DeviceArray, output: DeviceArray,
+              ctx: Optional[Context] = None) -> int:
+        """The filter's `apply` over device-resident arrays; returns K'."""
+        x, dtype_in = _info_run(input)
+        return self._run(x, dtype_in, output.data, output.dtype, ctx)
+
+
+def label_size_filter(labels, min_size: int = 1, max_size: Optional[int] = None,
+                      relabel: bool = True, dtype_out: Optional[str] = None,
+                      ctx: Optional[Context] = None):
+    """LabelSizeFilter(min_size, max_size, relabel).apply_ndarray(labels): (out, K')."""
+    return LabelSizeFilter(min_size, max_size, relabel).apply_ndarray(labels, dtype_out, ctx)
 
 
 class Downsample:

@@ -625,6 +625,126 @@ def distance_transform(input_path, output_path, spacing=None, squared: bool = Fa
     return st
 
 
+def label_size_filter_output(input_data_type: str, data_type: Optional[str] = None,
+                             encoding=None):
+    """(output data type, encoding) of a size filter's output array: an explicit data type
+    (`data_type` or the encoding's) wins, else the input's; the fill value is 0 unless given."""
+    enc = dict(encoding) if isinstance(encoding, dict) else (
+        json.loads(encoding) if encoding else {})
+    dt = enc.get("data_type") or data_type or input_data_type
+    enc["data_type"] = dt
+    if enc.get("fill_value") is None:
+        enc["fill_value"] = 0
+    return dt, enc
+
+
+class SizeFilterStep:
+    """LabelSizeFilter as a whole-array step drives it. The scratch depends on the largest label,
+    which is known only once the array is on the device; the budget takes the largest it can be:
+    the input type's maximum, the limit on labels, and (a label array made by
+    connected_components never exceeds it) the element count."""
+
+    def __init__(self, filt):
+        self.filt = filt
+        self.min_size, self.max_size, self.relabel = filt.min_size, filt.max_size, filt.relabel
+
+    def is_compatible(self, dtype_in, dtype_out) -> None:
+        self.filt.is_compatible(dtype_in, dtype_out)
+
+    def memory(self, dtype_in, dtype_out, shape) -> int:
+        n = int(np.prod(shape)) if len(shape) else 0
+        k = min(int(np.iinfo(NUMPY[dtype_in]).max), _abi.LABELS_MAX, max(n, 1))
+        return self.filt.memory(dtype_in, dtype_out, shape, k)
+
+    def apply(self, input, output, ctx=None):
+        return self.filt.apply(input, output, ctx=ctx)
+
+
+def label_size_filter(input_path, output_path, min_size: int = 1, max_size: Optional[int] = None,
+                      relabel: bool = True, data_type: Optional[str] = None, device: int = 0,
+                      nthreads: int = 0, encoding=None) -> dict:
+    """zarrs_filter label-size-filter INPUT OUTPUT [--min-size N] [--max-size N] [--no-relabel]
+    [--data-type T]: keeps the labels of an integer label array whose element count lies in [min_size,
+    max_size] and sets every other label to 0 (filter.LabelSizeFilter; the input's data type and
+    fill value 0 unless given); with `relabel` the kept labels are renumbered 1 .. K'. A label may
+    span every chunk, so the whole array is read into device memory, filtered there and written
+    once; an array that does not fit 80 % of the free device memory fails with
+    ZT_ERR_OUT_OF_MEMORY before anything is read. When the largest output label does not fit the
+    output type, or an element is negative, the step fails with InvalidParameters, writes no chunk
+    and publishes no zarr.json. Returns the run stats and "components": K'."""
+    import time
+    from . import filter as F
+    t0 = time.perf_counter()
+    info = open_array(input_path)
+    filt = F.LabelSizeFilter(min_size, max_size, relabel)
+    dt, enc = label_size_filter_output(info.data_type, data_type, encoding)
+    filt.is_compatible(info.data_type, dt)
+    st, k = _whole_array_step(
+        input_path, output_path, info, SizeFilterStep(filt), dt, enc, device, nthreads, t0,
+        "input, output, the counts and the remap table of the most labels the input can hold",
+        "label_size_filter counts every label over the whole array in device memory (a label "
+        "may span every chunk): there is no store -> store path to fall back to")
+    st["components"] = int(k)
+    return st
+
+
+def label_statistics(labels_path, intensity_path=None, n_labels: Optional[int] = None,
+                     device: int = 0, nthreads: int = 0) -> dict:
+    """zarrs_info PATH label-statistics [--intensity PATH] [--n-labels K]: the per-label count,
+    bounding box, coordinate sums and centroid of an integer label array, and with an intensity
+    array of the same shape (any chunk grid and codecs) the smallest, largest, summed and mean
+    intensity (filter.LabelStatistics, whose result dict this returns). Only elements inside the
+    shape count and a missing chunk is its fill value. Both arrays are read into device memory;
+    arrays (and, with n_labels given, the state) that do not fit 80 % of the free device memory
+    fail with ZT_ERR_OUT_OF_MEMORY before anything is read; with n_labels=None the state is
+    budgeted once the range reduction has given the largest label."""
+    from . import filter as F
+    from .device_io import read_to_device
+    info = open_array(labels_path)
+    iinfo = open_array(intensity_path) if intensity_path is not None else None
+    filt = F.LabelStatistics(n_labels)
+    filt.is_compatible(info.data_type, iinfo.data_type if iinfo else None)
+    shape = [int(s) for s in info.shape]
+    if iinfo is not None and [int(s) for s in iinfo.shape] != shape:
+        raise _abi.InvalidParameters(
+            _abi.ERR_INVALID_PARAMETERS,
+            f"Array shapes do not match: {shape} vs {[int(s) for s in iinfo.shape]}")
+    n = int(np.prod(shape)) if shape else 0
+    arrays = n * NUMPY[info.data_type]().itemsize + \
+        (n * NUMPY[iinfo.data_type]().itemsize if iinfo else 0)
+    budget = device_available_bytes(device) // 10 * 8
+
+    def refuse(need, k, hint):
+        raise _abi.FilterError(
+            _abi.ERR_OUT_OF_MEMORY,
+            "There is not enough available memory to process the array: it needs "
+            f"{need} bytes of device memory (labels, intensities and the state of {k} "
+            f"labels) and 80 % of the available memory is {budget}; label_statistics reduces "
+            f"the whole array in device memory{hint}")
+
+    # budget, before anything is read: the arrays, and the state when n_labels says how large it
+    # is; with n_labels=None the state is budgeted once the range reduction has given K
+    state = filt.state_bytes(info.ndim, n_labels, iinfo is not None) if n_labels is not None else 0
+    if arrays + state > budget:
+        refuse(arrays + state, n_labels if n_labels is not None else "the", "")
+    x = read_to_device(labels_path, device, nthreads)
+    y = read_to_device(intensity_path, device, nthreads) if iinfo else None
+    ctx = F.default_context(device)
+    lab = F.DeviceArray(x, info.chunk_shape, info.data_type)
+    if n_labels is None:
+        k = filt.largest_label(lab, ctx)
+        if k > _abi.LABELS_MAX:
+            raise _abi.InvalidParameters(
+                _abi.ERR_INVALID_PARAMETERS,
+                f"label_statistics: n_labels {k} not in [0, {_abi.LABELS_MAX}]")
+        state = filt.state_bytes(info.ndim, k, iinfo is not None)
+        if arrays + state > budget:
+            refuse(arrays + state, k, ": pass a smaller n_labels only if the labels allow it")
+        filt = F.LabelStatistics(k)
+    return filt.apply_ndarray(lab, None if y is None else
+                              F.DeviceArray(y, iinfo.chunk_shape, iinfo.data_type), ctx)
+
+
 def pointwise_output(filt, input_data_type: str, data_type: Optional[str] = None, encoding=None):
     """(output data type, encoding) of a per-element filter's output array, as
     output_array_builder decides it (filter_traits.rs:47-82): an explicit data type (`data_type`

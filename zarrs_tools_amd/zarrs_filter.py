@@ -1,7 +1,7 @@
 """``zarrs_filter`` for the on-path filters (guided_filter, downsample, gaussian,
 summed_area_table, the rank filters median, minimum, maximum, the per-element reencode, crop,
 rescale, clamp, equal, replace_value, the two-array arithmetic and the whole-array
-connected_components and distance_transform) over Zarr V3 stores.
+connected_components, distance_transform and label_size_filter) over Zarr V3 stores.
 
 Mirrors src/bin/zarrs_filter.rs (LDeakin/zarrs_tools 0.7.2) for the filters this framework
 accelerates:
@@ -22,7 +22,9 @@ accelerates:
                                         | connected-components IN OUT [--connectivity C]
                                               [--data-type T]
                                         | distance-transform IN OUT [--spacing S[,S...]]
-                                              [--squared] [--data-type T]]
+                                              [--squared] [--data-type T]
+                                        | label-size-filter IN OUT [--min-size N] [--max-size N]
+                                              [--no-relabel] [--data-type T]]
 
 * subcommand arguments as GuidedFilterArguments (guided_filter.rs:25-33),
   DownsampleArguments (downsample.rs:20-33, STRIDE comma delimited) and GaussianArguments
@@ -51,12 +53,18 @@ accelerates:
   axis, comma delimited integers >= 1, one per axis (default all 1); --squared stores the squared
   distance, an exact integer; OUT is float32 (uint32 with --squared) with fill value 0 unless
   --data-type names another numeric type;
+  label-size-filter (an extension: the reference has none) keeps the labels of
+  an integer label array (0 = background) whose element count lies in [--min-size, --max-size]
+  (default 1 and no bound) and sets every other label to 0; the kept labels are renumbered
+  1 .. K' in increasing order of their old value unless --no-relabel; OUT has IN's type and fill
+  value 0 unless --data-type names another integer type, and the step fails, writing nothing,
+  when the largest output label does not fit it or an element is negative; the step logs K';
 * a JSON run config is a list of {"filter": "guided_filter" | "downsample" | "gaussian" |
   "summed_area_table" | "median" | "minimum" | "maximum" | "reencode" | "crop" | "rescale" |
   "clamp" | "equal" | "replace_value" | "arithmetic" | "connected_components" |
-  "distance_transform", "input", "output", ...args (kernel_half_size; offset, shape, multiply, add, add_first, min, max, value, replace
+  "distance_transform" | "label_size_filter", "input", "output", ...args (kernel_half_size; offset, shape, multiply, add, add_first, min, max, value, replace
   for the per-element filters; connectivity for connected_components; spacing, squared for
-  distance_transform; operator, other for
+  distance_transform; min_size, max_size, relabel for label_size_filter; operator, other for
   arithmetic, whose "other" is a path or the
   "$name" of a temporary that an earlier step wrote), "data_type"}, with "$name" meaning a named
   temporary array under --tmp and an omitted input meaning the previous filter's output (zarrs_filter.rs:106-138,
@@ -89,7 +97,7 @@ accelerates:
 gradient_magnitude is rejected with FilterError::Other: it runs from the library only
 (DESIGN.md §1). A summed-area table's chunk rows each need the previous row's last plane, so with
 --gpus > 1 that step runs in one process on the first device (`rows_splittable`); so do
-connected_components and distance_transform, whose unit of work is the whole array: it is read
+connected_components, distance_transform and label_size_filter, whose unit of work is the whole array: it is read
 into device memory, processed and written once, and fails with the out-of-memory error when it
 does not fit (there is no store -> store path for them). The other
 filters' rows, the per-element ones included, are split over the processes. `--chunk-limit N`
@@ -120,7 +128,7 @@ POINTWISE = ("reencode", "crop", "rescale", "clamp", "equal", "replace_value")
 RANK = ("median", "minimum", "maximum")
 BINARY = ("arithmetic",)  # two arrays in: "input" and "other"
 # no chunk rows at all: the array is the unit of work
-WHOLE_ARRAY = ("connected_components", "distance_transform")
+WHOLE_ARRAY = ("connected_components", "distance_transform", "label_size_filter")
 ON_PATH = ("guided_filter", "downsample", "gaussian", "summed_area_table") + RANK + POINTWISE + \
     BINARY + WHOLE_ARRAY
 
@@ -316,6 +324,18 @@ def build_parser() -> argparse.ArgumentParser:
     dtr.add_argument("--squared", action="store_true",
                      help="store the squared distance (an exact integer; uint32 by default)")
     _add_reencode_args(dtr)
+    lsf = sub.add_parser("label-size-filter",
+                         help="Keep the labels of a label array whose element count is in range.")
+    lsf.add_argument("input")
+    lsf.add_argument("output")
+    lsf.add_argument("--min-size", type=int, default=1,
+                     help="the fewest elements of a label that is kept (default 1)")
+    lsf.add_argument("--max-size", type=int, default=None,
+                     help="the most elements of a label that is kept (default: no bound)")
+    lsf.add_argument("--no-relabel", action="store_true",
+                     help="kept labels keep their values (default: renumbered 1 .. K' in "
+                          "increasing order)")
+    _add_reencode_args(lsf)
     return ap
 
 
@@ -360,6 +380,11 @@ def _steps_from_cli(a) -> list:
         return [{"filter": "distance_transform", "input": a.input, "output": a.output,
                  "spacing": a.spacing, "squared": a.squared, "data_type": a.data_type,
                  "chunk_limit": a.filter_chunk_limit, **_reencode_of(a)}]
+    if a.filter == "label-size-filter":
+        return [{"filter": "label_size_filter", "input": a.input, "output": a.output,
+                 "min_size": a.min_size, "max_size": a.max_size, "relabel": not a.no_relabel,
+                 "data_type": a.data_type, "chunk_limit": a.filter_chunk_limit,
+                 **_reencode_of(a)}]
     return []
 
 
@@ -459,7 +484,24 @@ def step_encoding(step: dict, in_data_type: str):
     if step.get("filter") == "distance_transform":  # float32, or uint32 squared; fill value 0
         _dt, enc = S.distance_transform_output(bool(step.get("squared", False)),
                                                step.get("data_type"), enc)
+    if step.get("filter") == "label_size_filter":  # the input's type; fill value 0
+        _dt, enc = S.label_size_filter_output(in_data_type, step.get("data_type"), enc)
     return enc
+
+
+def label_size_filter_of(step: dict):
+    """The size filter of a run-config step: "min_size" (default 1) and "max_size" (default
+    none) integers, "relabel" a boolean (default true)."""
+    from . import filter as F
+    try:
+        mn = 1 if step.get("min_size") is None else int(step["min_size"])
+        mx = None if step.get("max_size") is None else int(step["max_size"])
+    except (TypeError, ValueError):
+        raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS,
+                                     "label_size_filter: min_size and max_size are "
+                                     "integers") from None
+    relabel = step.get("relabel")
+    return S.SizeFilterStep(F.LabelSizeFilter(mn, mx, True if relabel is None else bool(relabel)))
 
 
 def connectivity_of(step: dict) -> int:
@@ -515,6 +557,12 @@ def _step_params(step, info):
         f.is_compatible(info.data_type, dt)
         f.check_spacing(info.ndim)
         f.memory(info.data_type, dt, info.shape)  # the bound on the squared distance
+        return f, tuple(info.shape), dt
+    if name == "label_size_filter":
+        f = label_size_filter_of(step)
+        dt, _enc = S.label_size_filter_output(info.data_type, step.get("data_type"),
+                                              encoding_of(step))
+        f.is_compatible(info.data_type, dt)
         return f, tuple(info.shape), dt
     dt = step.get("data_type") or (encoding_of(step) or {}).get("data_type") or info.data_type
     if name == "guided_filter":
@@ -666,7 +714,7 @@ def run_device_chain(steps: list, paths: list, device: int = 0, nthreads: int = 
         log(f"{i if j == i else f'{i}-{j}'}: {names} device-resident {list(x.shape)} {x_dt} -> "
             f"{list(y.shape)} {out_info.data_type} in {t_k:.3f}s")
         components = None
-        if names == "connected_components":  # only the labelling has a count
+        if names in ("connected_components", "label_size_filter"):  # the steps with a count
             components = int(ret)
             log(f"   {components} components")
         if names in WHOLE_ARRAY:
@@ -896,6 +944,10 @@ def run(steps: list, exists: str = "erase", tmp: str | None = None,
                       "squared": f.squared}
             log(f"{i}: distance_transform spacing={params['spacing'] or 'ones'} "
                 f"squared={f.squared} {src} ({info.data_type} {list(info.shape)}) -> {dst}")
+        elif name == "label_size_filter":
+            params = {"min_size": f.min_size, "max_size": f.max_size, "relabel": f.relabel}
+            log(f"{i}: label_size_filter min_size={f.min_size} max_size={f.max_size} "
+                f"relabel={f.relabel} {src} ({info.data_type} {list(info.shape)}) -> {dst}")
         else:
             params = {"stride": list(f.stride), "discrete": bool(step.get("discrete", False))}
             log(f"{i}: downsample stride={params['stride']} discrete={params['discrete']} "
@@ -911,6 +963,10 @@ def run(steps: list, exists: str = "erase", tmp: str | None = None,
                 return S.distance_transform(src, dst, params["spacing"], params["squared"],
                                             data_type=params["data_type"], device=dev,
                                             encoding=enc)
+            if name == "label_size_filter":
+                return S.label_size_filter(src, dst, params["min_size"], params["max_size"],
+                                           params["relabel"], data_type=params["data_type"],
+                                           device=dev, encoding=enc)
             return S.summed_area_table(src, dst, data_type=params["data_type"], device=dev,
                                        encoding=enc, chunk_limit=limit)
 

@@ -3,7 +3,8 @@
     zarrs_info [--chunk-limit N] [--device D] PATH COMMAND
 
 COMMAND (zarrs_info.rs:42-62): metadata, metadata-v3, attributes, shape, data-type, fill-value,
-dimension-names, range, histogram N_BINS MIN MAX. The first seven read zarr.json and need no GPU;
+dimension-names, range, histogram N_BINS MIN MAX, and the extension label-statistics [--intensity
+PATH] [--n-labels K] [--max-labels N] (DESIGN.md §3.15). The first seven read zarr.json and need no GPU;
 metadata, metadata-v3 and attributes also work on a group (:92-109). `range` and `histogram` run
 the store path's reductions on the GPU (store.range / store.histogram; src/info/range.rs,
 src/info/histogram.rs). The store is V3 only, so metadata-v3 prints the document of metadata
@@ -28,7 +29,9 @@ from . import _abi
 GROUP_COMMANDS = ("metadata", "metadata-v3", "attributes")
 # `{:?}` of the InfoCommand variants (zarrs_info.rs:106-108)
 _DEBUG_NAMES = {"shape": "Shape", "data-type": "DataType", "fill-value": "FillValue",
-                "dimension-names": "DimensionNames", "range": "Range"}
+                "dimension-names": "DimensionNames", "range": "Range",
+                "label-statistics": "LabelStatistics"}
+DEFAULT_MAX_LABELS = 1_000_000
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -54,6 +57,14 @@ def build_parser() -> argparse.ArgumentParser:
     h.add_argument("n_bins", type=int)
     h.add_argument("min", type=float)
     h.add_argument("max", type=float)
+    ls = sub.add_parser("label-statistics",
+                        help="Get the per-label statistics of an integer label array.")
+    ls.add_argument("--intensity", default=None, metavar="PATH",
+                    help="An array of the same shape whose values are reduced per label.")
+    ls.add_argument("--n-labels", type=int, default=None, metavar="K",
+                    help="The number of labels (default: the largest label present).")
+    ls.add_argument("--max-labels", type=int, default=DEFAULT_MAX_LABELS, metavar="N",
+                    help="Refuse to print more than N labels.")
     return ap
 
 
@@ -68,6 +79,42 @@ def json_number(x):
     if isinstance(x, float) and math.isinf(x):
         return "Infinity" if x > 0 else "-Infinity"
     return x
+
+
+def _json_column(values):
+    """A column for JSON: integers as integers, floats through json_number, NaN as null."""
+    out = []
+    for v in values.tolist():
+        if isinstance(v, list):
+            out.append([None if isinstance(x, float) and math.isnan(x) else json_number(x)
+                        for x in v])
+        else:
+            out.append(None if isinstance(v, float) and math.isnan(v) else json_number(v))
+    return out
+
+
+def label_statistics_json(res: dict) -> dict:
+    """The result of store.label_statistics as a JSON document: the columns indexed by label - 1;
+    an absent label has null bounds and centroid, a label with no non-NaN intensity null minimum
+    and maximum, the types without sums a null column."""
+    present = (res["count"] != 0).tolist()
+    doc = {"n_labels": res["n_labels"], "background": res["background"],
+           "count": [int(c) for c in res["count"]]}
+    for key in ("bbox_min", "bbox_max"):
+        doc[key] = [row if p else None for row, p in zip(res[key].tolist(), present)]
+    doc["coord_sum"] = [[int(x) for x in row] for row in res["coord_sum"].tolist()]
+    doc["centroid"] = [row if p else None
+                       for row, p in zip(_json_column(res["centroid"]), present)]
+    if "intensity_min" in res:
+        valid = res["intensity_valid"].tolist()
+        for key in ("intensity_min", "intensity_max"):
+            col = _json_column(res[key].astype(float) if res[key].dtype.kind == "f" else res[key])
+            doc[key] = [v if ok else None for v, ok in zip(col, valid)]
+        doc["intensity_sum"] = None if res["intensity_sum"] is None else \
+            [int(v) for v in res["intensity_sum"]]
+        doc["intensity_mean"] = None if res["intensity_mean"] is None else \
+            _json_column(res["intensity_mean"])
+    return doc
 
 
 def _debug_command(a) -> str:
@@ -123,6 +170,21 @@ def run(a) -> str:
     if a.command == "range":
         lo, hi = store.range(a.path, device=a.device, chunk_limit=a.chunk_limit)
         return _pretty({"min": json_number(lo), "max": json_number(hi)})
+    if a.command == "label-statistics":
+        if a.n_labels is not None and a.n_labels > a.max_labels:
+            raise _abi.InvalidParameters(
+                _abi.ERR_INVALID_PARAMETERS,
+                f"label-statistics: {a.n_labels} labels are more than --max-labels "
+                f"{a.max_labels}; raise it, or use zarrs_tools_amd.store.label_statistics, which "
+                "returns the columns as numpy arrays")
+        res = store.label_statistics(a.path, a.intensity, a.n_labels, device=a.device)
+        if res["n_labels"] > a.max_labels:
+            raise _abi.InvalidParameters(
+                _abi.ERR_INVALID_PARAMETERS,
+                f"label-statistics: {res['n_labels']} labels are more than --max-labels "
+                f"{a.max_labels}; raise it, or use zarrs_tools_amd.store.label_statistics, which "
+                "returns the columns as numpy arrays")
+        return _pretty(label_statistics_json(res))
     edges, hist = store.histogram(a.path, a.n_bins, a.min, a.max, device=a.device,
                                   chunk_limit=a.chunk_limit)
     return _pretty({"bin_edges": [float(e) for e in edges], "hist": [int(h) for h in hist]})
