@@ -537,6 +537,56 @@ int zt_label_size_filter_apply_array(zt_ctx* ctx, int dtype_in, const void* in, 
                                      void* out, const int64_t* shape, int ndim, int64_t min_size,
                                      int64_t max_size, int relabel, uint64_t* kept);
 
+/* ---- morphological reconstruction (an extension: the reference has no such filter) ------------- */
+
+/* Reconstruction of a marker under a mask, both of one shape and one element type. Elements are
+ * only selected, under the rank filters' total order (unsigned and signed integer order, false <
+ * true, floats -NaN < -inf < ... < -0.0 < +0.0 < ... < +inf < +NaN): every output element carries
+ * the storage bits of some marker or mask element. Two elements are neighbours when their
+ * coordinates differ by at most 1 on every axis and on at most `connectivity` axes (nothing wraps
+ * or replicates at the edges). By dilation: J0 = min(marker, mask) (a marker above the mask is
+ * clipped, not an error) and out is the least J >= J0 with J[p] = min(max(J[q] : q = p or a
+ * neighbour of p), mask[p]) for every p. By erosion: the same with the order reversed. The marker
+ * modes other than ZT_REC_MARKER make the marker from the mask on the device: ZT_REC_FILL_HOLES
+ * (by erosion; the mask where any coordinate is 0 or extent - 1, the type's greatest key
+ * elsewhere), ZT_REC_H_MAXIMA (by dilation; (mask as f64 - h) as T, the arithmetic filter's
+ * subtract) and ZT_REC_H_MINIMA (by erosion; (mask as f64 + h) as T). Semantics, kernels and the
+ * termination argument: DESIGN.md §3.16. */
+/* The tile of the three innermost axes that one workgroup of a round owns, and the rounds the host
+ * launches between two reads of their flag words. */
+#define ZT_REC_TILE_Z 8
+#define ZT_REC_TILE_Y 8
+#define ZT_REC_TILE_X 32
+#define ZT_REC_BATCH 8
+enum { ZT_REC_DILATION = 0, ZT_REC_EROSION = 1 };
+enum { ZT_REC_MARKER = 0, ZT_REC_FILL_HOLES = 1, ZT_REC_H_MAXIMA = 2, ZT_REC_H_MINIMA = 3 };
+/* An extension. All 13 types; a marker type other than the mask's (read with ZT_REC_MARKER only)
+ * and bool with the two h modes are ZT_ERR_UNSUPPORTED_DATA_TYPE; an unknown marker mode is
+ * ZT_ERR_INVALID_PARAMETERS. */
+int zt_reconstruction_is_compatible(int dtype_mask, int dtype_marker, int marker_mode);
+/* An extension. Device bytes of one call: input(s) + scratch + output = n * size for the mask, as
+ * much again for a marker array (ZT_REC_MARKER only) and for the output, and the scratch: one
+ * working array of n * size bytes rounded up to 16, and 64 bytes of flag words. 0 for an array
+ * with a zero extent. A rank that the call refuses (below) is ZT_ERR_INVALID_PARAMETERS here
+ * too. */
+int zt_reconstruction_memory(int dtype, int marker_mode, const int64_t* shape, int ndim,
+                             uint64_t* bytes);
+/* An extension. Reconstructs on the whole C-order device arrays `mask` and `marker` (shape[ndim],
+ * element alignment; `marker` is read with ZT_REC_MARKER only and may be NULL otherwise) into
+ * `out` (same shape and type, not overlapping them) on the context's stream. `method` (ZT_REC_
+ * DILATION / EROSION) counts with ZT_REC_MARKER only; `h` (finite, > 0) with the two h modes only.
+ * connectivity outside [1, ndim], a rank above 3 with an axis in front of the innermost three
+ * whose extent is not 1, more than 2^38 elements or 2^31 - 1 tiles are
+ * ZT_ERR_INVALID_PARAMETERS, before anything is written. Rounds alternate between `out` and the
+ * scratch array, ZT_REC_BATCH at a time, each with its own flag word; the call synchronises the
+ * stream once per batch to read the flags, and stops at the first round that changed nothing
+ * (*rounds, may be NULL, counts it). ZT_REC_TILE_SWEEPS=N (read at every call) caps the sweeps of a
+ * tile per round; more than n + 1 rounds are ZT_ERR_OTHER. A refused scratch allocation is
+ * ZT_ERR_OUT_OF_MEMORY. A zero extent is a no-op with 0 rounds. There is no per-chunk form. */
+int zt_reconstruction_apply_array(zt_ctx* ctx, int dtype, const void* mask, const void* marker,
+                                  int marker_mode, double h, void* out, const int64_t* shape,
+                                  int ndim, int connectivity, int method, uint64_t* rounds);
+
 /* ---- zarrs_info reductions (src/info/range.rs, src/info/histogram.rs) ------------------------ */
 
 /* The 12 numeric types; ZT_BOOL is ZT_ERR_UNSUPPORTED_DATA_TYPE (the reference reaches

@@ -39,6 +39,13 @@ alternated with Range on the same arrays.
 floor); with scipy installed and a volume of at most 512^3, scipy.ndimage.distance_transform_edt
 on the host as the CPU baseline (`--no-scipy` skips it); `--edt-once` calls every transform once
 and nothing else, for a kernel trace.
+`--only reconstruction`: morphological reconstruction (reconstruct.hip) on 1024^3: fill_holes at
+connectivity 1 and 3 on the labelling's three uint8 volumes and h_maxima on the uint32 squared
+distance map of one of them, alternated with the connected_components call on the same volume and
+the Reencode uint8 -> uint32 cast; rounds, ms per call and ms per round against the streaming
+floor of a round (two reads and one write per element); with scipy installed,
+scipy.ndimage.binary_fill_holes on the host fills the same masks at `--rec-scipy-size`^3 (default
+256; `--no-scipy` skips it); `--rec-once` calls every case once and nothing else.
 
 Algorithmic bytes: pyramid = level 0 read once + every level written once (2 B per u16
 element; the fused launches never read an intermediate level back); Gaussian = 4 B read + 4 B written per voxel (the separable passes' intermediates are
@@ -1107,6 +1114,143 @@ def bench_distance_transform(n, rounds=5, window_s=0.5, scipy_baseline=True, onc
     return res
 
 
+def bench_reconstruction(n, rounds=3, window_s=0.5, scipy_size=256, once=False):
+    """Morphological reconstruction (reconstruct.hip) on n^3 device arrays: fill_holes at
+    connectivity 1 and 3 on the labelling's three uint8 volumes (noise 0.05, noise 0.6, synth_u16
+    above its 0.7 quantile) and h_maxima (h = 1, connectivity 1) on the uint32 squared distance map
+    of the blobs volume, alternated in one run with two yardsticks: the connected_components call
+    on the same volume and the Reencode uint8 -> uint32 cast. Windows of at least window_s after a
+    warm-up, `rounds` of each, medians. Every call synchronises the stream once per batch of
+    rounds; those waits are inside the windows. Reported per case: the rounds of the call, ms per
+    call, ms per round, and the streaming floor of a round (two reads and one write per element
+    at HBM_PEAK_GBS). With scipy installed and scipy_size > 0, the same three masks at
+    scipy_size^3 are filled on the host by scipy.ndimage.binary_fill_holes (its time, and equality
+    with the device's result on that volume). once=True: every case called once and nothing else
+    (for a kernel trace)."""
+    import math
+    import numpy as np
+    import torch
+    import zarrs_tools_amd as zt
+    ctx = zt.default_context(0)
+    stream = torch.cuda.current_stream()
+    chunk = (32, 32, 32)
+
+    def masks(m):
+        shape, total = (m, m, m), m ** 3
+        gen = torch.Generator(device="cuda").manual_seed(2025)
+        noise = torch.rand(shape, device="cuda", generator=gen)
+        u16 = zt.synth_u16(shape)
+        sample = u16.reshape(-1)[:: max(1, total // (1 << 20))].to(torch.float32)
+        level = float(torch.quantile(sample, 0.7))
+        return {"sparse_0.05": (noise < 0.05).to(torch.uint8),
+                "dense_0.6": (noise < 0.6).to(torch.uint8),
+                "blobs": (u16.to(torch.float32) > level).to(torch.uint8)}
+
+    shape, total = (n, n, n), n ** 3
+    volumes = masks(n)
+    out8 = torch.empty(shape, dtype=torch.uint8, device="cuda")
+    out32 = torch.empty(shape, dtype=torch.uint32, device="cuda")
+    d2 = torch.empty(shape, dtype=torch.uint32, device="cuda")
+    zt.DistanceTransform(None, True).apply(zt.DeviceArray(volumes["blobs"], chunk, "uint8"),
+                                           zt.DeviceArray(d2, chunk, "uint32"), ctx=ctx)
+    ctx.synchronize()
+    ctx.release_scratch()
+    cast = zt.PointwiseProgram([zt.Reencode()], "uint8", ["uint32"], shape)
+    fills = {c: zt.Reconstruction(mode="fill_holes", connectivity=c) for c in (1, 3)}
+    hmax = zt.Reconstruction(mode="h_maxima", h=1.0)
+    cc = zt.ConnectedComponents(1)
+
+    def fill(v, c, out=None):
+        return fills[c].apply(zt.DeviceArray(v, chunk, "uint8"),
+                              zt.DeviceArray(out8 if out is None else out, chunk, "uint8"),
+                              ctx=ctx)
+
+    def h_maxima():
+        return hmax.apply(zt.DeviceArray(d2, chunk, "uint32"),
+                          zt.DeviceArray(out32, chunk, "uint32"), ctx=ctx)
+
+    ops, counts, esz = {}, {}, {}
+    for name, v in volumes.items():
+        ops[f"{name}_cast_u8_u32"] = (lambda v=v: cast.run(v, out32, ctx))
+        ops[f"{name}_connected_components_c1"] = (
+            lambda v=v: cc.apply(zt.DeviceArray(v, chunk, "uint8"),
+                                 zt.DeviceArray(out32, chunk, "uint32"), ctx=ctx))
+        for c in (1, 3):
+            ops[f"{name}_fill_holes_c{c}"] = (lambda v=v, c=c: fill(v, c))
+            esz[f"{name}_fill_holes_c{c}"] = 1
+    ops["blobs_d2_u32_h_maxima_1_c1"] = h_maxima
+    esz["blobs_d2_u32_h_maxima_1_c1"] = 4
+    first_s = {}
+    for k in esz:
+        t0 = time.perf_counter()
+        counts[k] = int(ops[k]())  # the rounds of the call
+        ctx.synchronize()
+        first_s[k] = round(time.perf_counter() - t0, 4)
+    if once:
+        return {"op": "reconstruction, one call each", "config": {"shape": [n] * 3},
+                "rounds": counts, "first_call_s": first_s}
+    reps = {}
+    for k, fn in ops.items():  # warm-up, then calls per window until it lasts window_s
+        r = 1
+        while True:
+            t = timed(fn, stream, r)
+            if t * r >= window_s * 1e3:
+                break
+            r = math.ceil(window_s * 1e3 / t * 1.05) + 1
+        reps[k] = r
+    ms = {k: [] for k in ops}
+    for _ in range(rounds):
+        for k, fn in ops.items():
+            ms[k].append(timed(fn, stream, reps[k]))
+    res = {"op": "reconstruction (device-resident)",
+           "config": {"shape": [n] * 3, "rounds": rounds, "window_s": window_s,
+                      "tile_sweeps": os.environ.get("ZT_REC_TILE_SWEEPS", "default")},
+           "foreground": {k: round(float(v.to(torch.float32).mean()), 4)
+                          for k, v in volumes.items()},
+           "ops": {}}
+    for k in ops:
+        v = sorted(ms[k])
+        med = v[len(v) // 2]
+        res["ops"][k] = {"ms": round(med, 4), "ms_min": round(v[0], 4), "ms_max": round(v[-1], 4),
+                         "spread": round((v[-1] - v[0]) / med, 4), "calls_per_window": reps[k]}
+        if k in counts:
+            floor = total * 3 * esz[k] / (HBM_PEAK_GBS * 1e9) * 1e3
+            name = k.split("_fill_holes")[0].split("_d2_")[0]
+            res["ops"][k].update({
+                "rounds_of_the_call": counts[k],
+                "ms_per_round": round(med / counts[k], 4),
+                "round_floor_ms": round(floor, 4),
+                "round_over_floor": round(med / counts[k] / floor, 2),
+                "ratio_to_cast": round(med / res["ops"][f"{name}_cast_u8_u32"]["ms"], 2),
+                "ratio_to_connected_components": round(
+                    med / res["ops"][f"{name}_connected_components_c1"]["ms"], 2)})
+    if scipy_size > 0:
+        try:
+            from scipy import ndimage
+        except ImportError:
+            ndimage = None
+        if ndimage is not None:
+            small = masks(scipy_size)
+            out = torch.empty((scipy_size,) * 3, dtype=torch.uint8, device="cuda")
+            res["scipy"] = {"shape": [scipy_size] * 3}
+            for name, v in small.items():
+                host = v.cpu().numpy()
+                for c in (1, 3):
+                    t0 = time.perf_counter()
+                    want = ndimage.binary_fill_holes(
+                        host, structure=ndimage.generate_binary_structure(3, c))
+                    dt = time.perf_counter() - t0
+                    ms_gpu = timed(lambda v=v, c=c: fill(v, c, out), stream, 3)
+                    got = out.cpu().numpy()
+                    res["scipy"][f"{name}_fill_holes_c{c}"] = {
+                        "scipy_s": round(dt, 3), "gpu_ms": round(ms_gpu, 3),
+                        "scipy_over_gpu": round(dt * 1e3 / ms_gpu, 1),
+                        "filled": int(want.sum() - host.sum()),
+                        "equals_scipy": bool(np.array_equal(got.astype(bool), want))}
+                    print(f"scipy {name} c{c}: {dt:.1f} s", file=sys.stderr, flush=True)
+    return res
+
+
 def bench_guided4d(shape, chunk, radius, reps):
     """Config T per GPU: a (T, Z, Y, X) f32 time-series share, chunks
     (4, 256, 256, 256), eps 2500. 4-D arrays take the separable per-axis path."""
@@ -1222,6 +1366,11 @@ def main():
     ap.add_argument("--edt-once", action="store_true",
                     help="distance_transform: call every transform once, nothing else (for a "
                          "kernel trace)")
+    ap.add_argument("--rec-once", action="store_true",
+                    help="reconstruction: call every case once, nothing else (for a kernel trace)")
+    ap.add_argument("--rec-scipy-size", type=int, default=256,
+                    help="reconstruction: the edge of the volumes that scipy.ndimage."
+                         "binary_fill_holes fills on the host (0 or --no-scipy skips it)")
     a = ap.parse_args()
     only = set(a.only.split(","))
     if "tshare" in only:
@@ -1272,6 +1421,10 @@ def main():
     if "distance_transform" in only:  # with the reencode uint8 -> float32 yardstick, alternated
         print(json.dumps(bench_distance_transform(
             a.gaussian_size, scipy_baseline=not a.no_scipy, once=a.edt_once)), flush=True)
+    if "reconstruction" in only:  # with the labelling and the reencode cast, alternated
+        print(json.dumps(bench_reconstruction(
+            a.gaussian_size, scipy_size=0 if a.no_scipy else a.rec_scipy_size,
+            once=a.rec_once)), flush=True)
 
 
 if __name__ == "__main__":

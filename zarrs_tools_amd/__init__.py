@@ -36,6 +36,7 @@ from .filter import (  # noqa: E402
     PointwiseProgram,
     Range,
     RankFilter,
+    Reconstruction,
     Reencode,
     ReplaceValue,
     Rescale,
@@ -74,4 +75,5 @@ __all__ = [
     "DistanceTransform",
     "LabelStatistics", "LabelSizeFilter", "combine_label_statistics", "label_statistics",
     "label_size_filter",
+    "Reconstruction",
 ]

@@ -84,6 +84,14 @@ AR_OPERATORS = {"add": 0, "subtract": 1, "multiply": 2, "divide": 3, "minimum": 
 # connected-component labelling owns; the scratch tail of a call (zt_connected_components_memory)
 CC_TILE = (8, 8, 64)
 
+# ZT_REC_TILE_Z / Y / X: the tile of the three innermost axes that one workgroup of a
+# reconstruction round owns; ZT_REC_BATCH: the rounds launched between two reads of their flag
+# words; ZT_REC_DILATION / EROSION and the marker modes ZT_REC_MARKER ... ZT_REC_H_MINIMA
+REC_TILE = (8, 8, 32)
+REC_BATCH = 8
+REC_METHODS = {"dilation": 0, "erosion": 1}
+REC_MODES = {"marker": 0, "fill_holes": 1, "h_maxima": 2, "h_minima": 3}
+
 
 # ZT_NO_DTYPE: the intensity type of a label statistics call without an intensity array;
 # ZT_LABELS_TILE_ROWS: the rows of a tile of its kernel (a tile is that many rows x 64 x)
@@ -263,6 +271,10 @@ def lib() -> ctypes.CDLL:
         "zt_label_size_filter_memory": ([c_int, c_int, i64p, c_int, ctypes.c_int64, u64p], c_int),
         "zt_label_size_filter_apply_array": ([vp, c_int, vp, c_int, vp, i64p, c_int,
                                               ctypes.c_int64, ctypes.c_int64, c_int, u64p], c_int),
+        "zt_reconstruction_is_compatible": ([c_int, c_int, c_int], c_int),
+        "zt_reconstruction_memory": ([c_int, c_int, i64p, c_int, u64p], c_int),
+        "zt_reconstruction_apply_array": ([vp, c_int, vp, vp, c_int, ctypes.c_double, vp, i64p,
+                                           c_int, c_int, c_int, u64p], c_int),
         "zt_range_is_compatible": ([c_int], c_int),
         "zt_histogram_is_compatible": ([c_int], c_int),
         "zt_range_init": ([vp, vp], c_int),

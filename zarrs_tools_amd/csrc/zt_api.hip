@@ -2007,6 +2007,132 @@ int zt_label_size_filter_apply_array(zt_ctx* ctx, int dtype_in, const void* in, 
     return ZT_OK;
 }
 
+// ---- morphological reconstruction (an extension; reconstruct.hip) --------------------------------
+
+static_assert(ZT_REC_TILE_Z == zt::kRecTileZ && ZT_REC_TILE_Y == zt::kRecTileY &&
+                  ZT_REC_TILE_X == zt::kRecTileX && ZT_REC_BATCH == zt::kRecBatch,
+              "the public header and the kernels agree on the tile and the batch");
+static_assert(ZT_REC_MARKER == zt::kRecMarker && ZT_REC_FILL_HOLES == zt::kRecFillHoles &&
+                  ZT_REC_H_MAXIMA == zt::kRecHMaxima && ZT_REC_H_MINIMA == zt::kRecHMinima,
+              "marker modes");
+static_assert(zt::kRecBatch * sizeof(uint32_t) <= zt::kRecTail, "the flag words fit the tail");
+
+int zt_reconstruction_is_compatible(int dtype_mask, int dtype_marker, int marker_mode) {
+    for (int d : {dtype_mask, dtype_marker})
+        if (!valid_dtype(d))
+            return fail(ZT_ERR_UNSUPPORTED_DATA_TYPE, "Unsupported data type code %d", d);
+    if (marker_mode < ZT_REC_MARKER || marker_mode > ZT_REC_H_MINIMA)
+        return fail(ZT_ERR_INVALID_PARAMETERS, "reconstruction: unknown marker mode %d",
+                    marker_mode);
+    if (marker_mode == ZT_REC_MARKER && dtype_marker != dtype_mask)
+        return fail(ZT_ERR_UNSUPPORTED_DATA_TYPE,
+                    "reconstruction: the marker is %s and the mask %s; they need one data type",
+                    dtype_name(dtype_marker), dtype_name(dtype_mask));
+    if ((marker_mode == ZT_REC_H_MAXIMA || marker_mode == ZT_REC_H_MINIMA) &&
+        dtype_mask == ZT_BOOL)
+        return fail(ZT_ERR_UNSUPPORTED_DATA_TYPE,
+                    "reconstruction: h_maxima and h_minima need a numeric type, not bool");
+    return ZT_OK;
+}
+
+int zt_reconstruction_memory(int dtype, int marker_mode, const int64_t* shape, int ndim,
+                             uint64_t* bytes) {
+    if (int rc = zt_reconstruction_is_compatible(dtype, dtype, marker_mode)) return rc;
+    if (int rc = check_shape(shape, ndim, "shape")) return rc;
+    if (!bytes) return fail(ZT_ERR_INVALID_PARAMETERS, "null pointer");
+    const int64_t n = numel(shape, ndim);
+    zt::RecGeom geom;
+    if (n != 0 && !zt::rec_geom(shape, ndim, &geom))
+        return fail(ZT_ERR_INVALID_PARAMETERS,
+                    "reconstruction: rank %d is supported only when every axis in front of the "
+                    "innermost three has extent 1", ndim);
+    const int esz = (int)zt::dtype_size(dtype);
+    const uint64_t arrays = marker_mode == ZT_REC_MARKER ? 3 : 2;  // mask, (marker,) output
+    *bytes = n == 0 ? 0 : arrays * (uint64_t)n * esz + zt::rec_scratch_bytes(n, esz);
+    return ZT_OK;
+}
+
+int zt_reconstruction_apply_array(zt_ctx* ctx, int dtype, const void* mask, const void* marker,
+                                  int marker_mode, double h, void* out, const int64_t* shape,
+                                  int ndim, int connectivity, int method, uint64_t* rounds) {
+    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = zt_reconstruction_is_compatible(dtype, dtype, marker_mode)) return rc;
+    if (int rc = check_shape(shape, ndim, "shape")) return rc;
+    if (connectivity < 1 || connectivity > ndim)
+        return fail(ZT_ERR_INVALID_PARAMETERS, "reconstruction: connectivity %d not in [1, %d]",
+                    connectivity, ndim);
+    if (marker_mode == ZT_REC_MARKER && method != ZT_REC_DILATION && method != ZT_REC_EROSION)
+        return fail(ZT_ERR_INVALID_PARAMETERS, "reconstruction: unknown method %d", method);
+    const bool h_mode = marker_mode == ZT_REC_H_MAXIMA || marker_mode == ZT_REC_H_MINIMA;
+    if (h_mode && !(std::isfinite(h) && h > 0))
+        return fail(ZT_ERR_INVALID_PARAMETERS, "reconstruction: h must be finite and > 0");
+    if (rounds) *rounds = 0;
+    const int64_t n = numel(shape, ndim);
+    if (n == 0) return ZT_OK;
+    zt::RecGeom geom;
+    if (!zt::rec_geom(shape, ndim, &geom))
+        return fail(ZT_ERR_INVALID_PARAMETERS,
+                    "reconstruction: rank %d is supported only when every axis in front of the "
+                    "innermost three has extent 1", ndim);
+    if (n > zt::kRecMaxElems)
+        return fail(ZT_ERR_INVALID_PARAMETERS, "reconstruction: %lld elements are more than %lld",
+                    (long long)n, (long long)zt::kRecMaxElems);
+    if (zt::rec_tiles(geom) > 0x7FFFFFFFll)
+        return fail(ZT_ERR_INVALID_PARAMETERS,
+                    "reconstruction: %lld tiles are more than one launch holds",
+                    (long long)zt::rec_tiles(geom));
+    const bool two = marker_mode == ZT_REC_MARKER;
+    if (!mask || !out || (two && !marker))
+        return fail(ZT_ERR_INVALID_PARAMETERS, "null data pointer");
+    if (mask == out || (two && marker == out))
+        return fail(ZT_ERR_INVALID_PARAMETERS, "input and output must differ");
+    const int esz = (int)zt::dtype_size(dtype);
+    if (((uintptr_t)mask % esz) != 0 || ((uintptr_t)out % esz) != 0 ||
+        (two && ((uintptr_t)marker % esz) != 0))
+        return fail(ZT_ERR_INVALID_PARAMETERS, "data pointers must be element aligned");
+    const bool erosion = two ? method == ZT_REC_EROSION : marker_mode != ZT_REC_H_MAXIMA;
+    const int sweeps = zt::rec_tile_sweeps();
+    DeviceGuard guard(ctx->device);
+    if (int rc = ctx->ensure_scratch((size_t)zt::rec_scratch_bytes(n, esz))) return rc;
+    if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev0, ctx->cur));
+    // buf[0] is the scratch array, buf[1] is `out`: round r reads buf[r % 2] and writes the other
+    void* buf[2] = {ctx->scratch, out};
+    uint32_t* flags = zt::rec_flags_ptr(ctx->scratch, n, esz);
+    hipError_t e = zt::launch_rec_init(mask, marker, buf[0], dtype, geom, marker_mode, h, erosion,
+                                       ctx->cur);
+    if (e != hipSuccess) return hip_fail(e, "reconstruction init launch");
+    // Every round but the last raises at least one element, so n + 1 rounds are a bound. Once a
+    // round has changed nothing the two buffers are equal; the rest of its batch does nothing.
+    uint64_t done = 0;
+    for (;;) {
+        ZT_HIP(hipMemsetAsync(flags, 0, zt::kRecBatch * sizeof(uint32_t), ctx->cur));
+        for (int k = 0; k < zt::kRecBatch; ++k) {
+            const uint64_t r = done + k;
+            e = zt::launch_rec_round(buf[r % 2], mask, buf[(r + 1) % 2], dtype, geom,
+                                     connectivity, erosion, sweeps, flags + k,
+                                     k ? flags + k - 1 : nullptr, ctx->cur);
+            if (e != hipSuccess) return hip_fail(e, "reconstruction round launch");
+        }
+        uint32_t host[zt::kRecBatch];
+        ZT_HIP(hipMemcpyAsync(host, flags, sizeof host, hipMemcpyDeviceToHost, ctx->cur));
+        ZT_HIP(hipStreamSynchronize(ctx->cur));
+        int quiet = -1;
+        for (int k = 0; k < zt::kRecBatch && quiet < 0; ++k)
+            if (host[k] == 0) quiet = k;
+        if (quiet >= 0) {
+            done += (uint64_t)quiet + 1;
+            break;
+        }
+        done += zt::kRecBatch;
+        if (done > (uint64_t)n)
+            return fail(ZT_ERR_OTHER, "reconstruction: no fixed point after %llu rounds of %lld "
+                        "elements", (unsigned long long)done, (long long)n);
+    }
+    if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev1, ctx->cur));
+    if (rounds) *rounds = done;
+    return ZT_OK;
+}
+
 // ---- zarrs_info reductions (range.rs, histogram.rs) --------------------------------------------
 
 namespace {

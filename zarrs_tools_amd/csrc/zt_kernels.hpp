@@ -318,6 +318,59 @@ hipError_t launch_lbl_keep_scan(const void* count_state, int64_t n_labels, uint6
 hipError_t launch_lbl_gather(const void* in, int dtype_in, const void* remap, void* out,
                              int dtype_out, int64_t n, hipStream_t s);
 
+// Morphological reconstruction (reconstruct.hip; an extension, no reference filter; DESIGN.md
+// §3.16) of a contiguous C-order array at element alignment, seen as its three innermost axes
+// (RecGeom: the axes in front of them all have extent 1). A workgroup of a round owns a tile of
+// kRecTileZ x kRecTileY x kRecTileX elements (ZT_REC_TILE_* in the public header) and sweeps it at
+// most rec_tile_sweeps() times (kRecTileSweeps: one crossing of the tile from corner to corner by
+// faces; ZT_REC_TILE_SWEEPS=N, read at every call). The host launches rounds in batches of
+// kRecBatch, each with its own flag word. Scratch (rec_scratch_bytes): one working array of the
+// element type, padded to 16 bytes, and the flag words. launch_rec_init writes
+// J0 = min(marker, mask) (max for erosion), or the generated marker of `marker_mode`, into `j0`;
+// launch_rec_round writes one round of `src` into `dst`, ORs 1 into *flag when a tile changed, and
+// does nothing when `prev` (the flag word of the round before, or NULL) is zero. Everything runs
+// on `s`; nothing synchronises.
+constexpr int kRecTileZ = 8, kRecTileY = 8, kRecTileX = 32;
+constexpr int kRecTileSweeps = kRecTileZ + kRecTileY + kRecTileX;
+constexpr int kRecBatch = 8;
+constexpr int kRecTail = 64;  // the flag words of a batch
+constexpr int64_t kRecMaxElems = (int64_t)1 << 38;
+enum RecMarkerMode : int { kRecMarker = 0, kRecFillHoles = 1, kRecHMaxima = 2, kRecHMinima = 3 };
+struct RecGeom {
+    int64_t Z, Y, X;  // the three innermost extents, padded in front with 1
+    int axes;         // how many of them are axes of the array: min(ndim, 3)
+    bool unit_front;  // ndim > 3 (every axis in front of them has extent 1)
+};
+// false when an axis in front of the innermost three has an extent other than 1
+inline bool rec_geom(const int64_t* shape, int ndim, RecGeom* g) {
+    for (int d = 0; d + 3 < ndim; ++d)
+        if (shape[d] != 1) return false;
+    g->X = shape[ndim - 1];
+    g->Y = ndim >= 2 ? shape[ndim - 2] : 1;
+    g->Z = ndim >= 3 ? shape[ndim - 3] : 1;
+    g->axes = ndim < 3 ? ndim : 3;
+    g->unit_front = ndim > 3;
+    return true;
+}
+inline int64_t rec_tiles(const RecGeom& g) {
+    return ((g.Z + kRecTileZ - 1) / kRecTileZ) * ((g.Y + kRecTileY - 1) / kRecTileY) *
+           ((g.X + kRecTileX - 1) / kRecTileX);
+}
+inline uint64_t rec_scratch_bytes(int64_t n, int esz) {
+    return (((uint64_t)n * (uint64_t)esz + 15) & ~(uint64_t)15) + kRecTail;
+}
+inline uint32_t* rec_flags_ptr(void* scratch, int64_t n, int esz) {
+    return reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(scratch) +
+                                       (rec_scratch_bytes(n, esz) - kRecTail));
+}
+int rec_tile_sweeps();
+hipError_t launch_rec_init(const void* mask, const void* marker, void* j0, int dtype,
+                           const RecGeom& geom, int marker_mode, double h, bool erosion,
+                           hipStream_t s);
+hipError_t launch_rec_round(const void* src, const void* mask, void* dst, int dtype,
+                            const RecGeom& geom, int connectivity, bool erosion, int sweeps,
+                            uint32_t* flag, const uint32_t* prev, hipStream_t s);
+
 // zarrs_info reductions (info.hip; src/info/range.rs, src/info/histogram.rs) over a contiguous
 // run of n elements of `dtype` (the 12 numeric types) at element alignment.
 // Range: `state` is two device u64 words (smallest key, largest key) that accumulate across

@@ -25,6 +25,8 @@ Names, argument meaning and error behaviour follow LDeakin/zarrs_tools 0.7.2:
     its semantics are DESIGN.md §3.12
   - ``ConnectedComponents``: an extension with no counterpart in the reference (labels of the
     connected sets of non-zero elements); its semantics are DESIGN.md §3.13
+  - ``Reconstruction``: an extension with no counterpart in the reference (morphological
+    reconstruction of a marker under a mask: fill holes, h-maxima, h-minima); DESIGN.md §3.16
   - ``DistanceTransform``: an extension with no counterpart in the reference (the exact Euclidean
     distance to the nearest zero element); its semantics are DESIGN.md §3.14
   - ``LabelStatistics``, ``LabelSizeFilter``: extensions with no counterpart in the reference
@@ -1831,6 +1833,134 @@ def label_size_filter(labels, min_size: int = 1, max_size: Optional[int] = None,
                       ctx: Optional[Context] = None):
     """LabelSizeFilter(min_size, max_size, relabel).apply_ndarray(labels): (out, K')."""
     return LabelSizeFilter(min_size, max_size, relabel).apply_ndarray(labels, dtype_out, ctx)
+
+
+class Reconstruction:
+    """An extension with no counterpart in the reference: morphological
+    reconstruction of a marker under a mask of the same shape and element type, any of the 13.
+    Elements are only selected, under the rank filters' total order; neighbours are the
+    labelling's (coordinates differ by at most 1 on every axis and on at most `connectivity`
+    axes). By dilation the result is the least J >= min(marker, mask) with J[p] = min(max(J over p
+    and its neighbours), mask[p]); a marker above the mask is clipped, not an error. By erosion the
+    order is reversed. `mode` "marker" takes a marker array; the other modes make the marker from
+    the mask on the device: "fill_holes" (by erosion; the mask on the array's border, the type's
+    greatest key elsewhere), "h_maxima" (by dilation; (mask as f64 - h) as T) and "h_minima" (by
+    erosion; (mask as f64 + h) as T), `h` a finite number > 0. `method` counts with "marker"
+    only. A whole-array operation: there is no per-chunk form."""
+
+    def __init__(self, method: str = "dilation", connectivity: int = 1, mode: str = "marker",
+                 h: Optional[float] = None):
+        self.method = str(method)
+        self.mode = str(mode).replace("-", "_")
+        self.connectivity = int(connectivity)
+        if self.mode not in _abi.REC_MODES:
+            raise _invalid(f"reconstruction: unknown mode {mode!r} (one of "
+                           f"{', '.join(_abi.REC_MODES)})")
+        if self.method not in _abi.REC_METHODS:
+            raise _invalid(f"reconstruction: unknown method {method!r} (dilation or erosion)")
+        implied = {"fill_holes": "erosion", "h_maxima": "dilation", "h_minima": "erosion"}
+        if self.mode != "marker":
+            if self.method not in ("dilation", implied[self.mode]):
+                raise _invalid(f"reconstruction: {self.mode} is by {implied[self.mode]}; a method "
+                               "is only given with a marker array")
+            self.method = implied[self.mode]
+        if self.connectivity < 1:
+            raise _invalid(f"reconstruction: connectivity {self.connectivity} not in [1, rank]")
+        if self.mode in ("h_maxima", "h_minima"):
+            try:
+                self.h = float(h)
+            except (TypeError, ValueError):
+                raise _invalid(f"reconstruction: {self.mode} needs a number h, not {h!r}") from None
+            if not (math.isfinite(self.h) and self.h > 0):
+                raise _invalid(f"reconstruction: h {self.h} is not a finite number > 0")
+        elif h is not None:
+            raise _invalid(f"reconstruction: h is only given with h_maxima or h_minima, not "
+                           f"{self.mode}")
+        else:
+            self.h = 0.0
+
+    def name(self) -> str:
+        return "reconstruction"
+
+    def check_connectivity(self, ndim: int) -> None:
+        """InvalidParameters unless 1 <= connectivity <= ndim."""
+        if not 1 <= self.connectivity <= int(ndim):
+            raise _invalid(f"reconstruction: connectivity {self.connectivity} not in "
+                           f"[1, {int(ndim)}]")
+
+    def is_compatible(self, dtype_mask: str, dtype_marker: Optional[str] = None) -> None:
+        """UnsupportedDataType when the marker's type is not the mask's, or for bool with h."""
+        check(lib().zt_reconstruction_is_compatible(
+            _info_dtype(dtype_mask), _info_dtype(dtype_marker or dtype_mask),
+            _abi.REC_MODES[self.mode]))
+
+    def memory(self, dtype_in: str, dtype_out: Optional[str], shape) -> int:
+        """Device bytes of one call on an array of `shape`: input(s) + scratch + output."""
+        self.is_compatible(dtype_in, dtype_out)
+        self.check_connectivity(len(shape))
+        out = ctypes.c_uint64()
+        check(lib().zt_reconstruction_memory(
+            _info_dtype(dtype_in), _abi.REC_MODES[self.mode], i64_array(shape), len(shape),
+            ctypes.byref(out)))
+        return int(out.value)
+
+    def _run(self, x, dtype, marker, out, dtype_out, ctx) -> int:
+        if self.mode == "marker":
+            if marker is None:
+                raise _invalid("reconstruction: mode marker needs a marker array")
+            m, dtype_marker = _info_run(marker)
+            if tuple(m.shape) != tuple(x.shape):
+                raise _invalid(f"Array shapes do not match: {list(x.shape)} vs {list(m.shape)}")
+            if m.device != x.device:
+                raise _invalid("reconstruction: the arrays are on different devices")
+        elif marker is not None:
+            raise _invalid(f"reconstruction: {self.mode} makes its marker from the mask; no "
+                           "marker array is given")
+        else:
+            m, dtype_marker = None, dtype
+        if tuple(out.shape) != tuple(x.shape):
+            raise _invalid(f"Array shapes do not match: {list(x.shape)} vs {list(out.shape)}")
+        if x.device != out.device:
+            raise _invalid("reconstruction: the arrays are on different devices")
+        if not out.is_contiguous():
+            raise _invalid("reconstruction: the output must be contiguous")
+        self.is_compatible(dtype, dtype_marker)
+        self.is_compatible(dtype, dtype_out)
+        self.check_connectivity(x.dim())
+        ctx = ctx or default_context(x.device.index)
+        rounds = ctypes.c_uint64()
+        check(lib().zt_reconstruction_apply_array(
+            ctx.handle, DTYPES[dtype], _ptr(x), _ptr(m) if m is not None else None,
+            _abi.REC_MODES[self.mode], self.h, _ptr(out), i64_array(x.shape), x.dim(),
+            self.connectivity, _abi.REC_METHODS[self.method], ctypes.byref(rounds)))
+        return int(rounds.value)
+
+    def apply_ndarray(self, mask, marker=None, ctx: Optional[Context] = None, out=None):
+        """Reconstructs on device tensors; returns (out, rounds). out is a new tensor of the mask's
+        type, or `out` (contiguous, of that type, not overlapping the inputs); rounds counts the
+        rounds up to and including the first that changed nothing. A bool array travels as a
+        uint8 tensor: it is named by a DeviceArray of data type bool, and then a tensor `out` of
+        the mask's torch type is taken to be bool too."""
+        x, dtype = _info_run(mask)
+        if out is None:
+            out = _torch().empty(tuple(x.shape), dtype=x.dtype, device=x.device)
+            dtype_out = dtype
+        elif isinstance(out, DeviceArray):
+            out, dtype_out = out.data, out.dtype
+        else:
+            dtype_out = dtype if out.dtype == x.dtype else dtype_of(out)
+        return out, self._run(x, dtype, marker, out, dtype_out, ctx)
+
+    def apply(self, mask: DeviceArray, marker: Optional[DeviceArray] = None,
+              output: Optional[DeviceArray] = None, ctx: Optional[Context] = None) -> int:
+        """The filter's `apply` over device-resident arrays; returns the rounds. The generated
+        marker modes may be called as apply(mask, output)."""
+        if output is None and self.mode != "marker":
+            marker, output = None, marker
+        if output is None:
+            raise _invalid("reconstruction: apply needs an output array")
+        x, dtype = _info_run(mask)
+        return self._run(x, dtype, marker, output.data, output.dtype, ctx)
 
 
 class Downsample:

@@ -688,6 +688,106 @@ def label_size_filter(input_path, output_path, min_size: int = 1, max_size: Opti
     return st
 
 
+def reconstruction_output(input_path, data_type: Optional[str] = None, encoding=None):
+    """(output data type, encoding) of a reconstruction's output array: the input's type (an
+    explicit other type is UnsupportedDataType) and, unless given, the input's fill value."""
+    enc = dict(encoding) if isinstance(encoding, dict) else (
+        json.loads(encoding) if encoding else {})
+    info = open_array(input_path)
+    dt = enc.get("data_type") or data_type or info.data_type
+    if dt != info.data_type:
+        raise _abi.UnsupportedDataType(
+            _abi.ERR_UNSUPPORTED_DATA_TYPE,
+            f"reconstruction: the output has the input's data type {info.data_type}, not {dt}")
+    enc["data_type"] = dt
+    return dt, enc
+
+
+class MarkerStep:
+    """Reconstruction with a marker array as a whole-array step drives it: the marker is read into
+    device memory after the mask (its bytes are in `memory`) and released with the step."""
+
+    def __init__(self, filt, marker_path, device: int, nthreads: int):
+        self.filt, self.marker_path = filt, marker_path
+        self.device, self.nthreads = device, nthreads
+
+    def memory(self, dtype_in, dtype_out, shape) -> int:
+        return self.filt.memory(dtype_in, dtype_out, shape)
+
+    def apply(self, input, output, ctx=None):
+        from . import filter as F
+        from .device_io import read_to_device
+        info = open_array(self.marker_path)
+        marker = read_to_device(self.marker_path, self.device, self.nthreads)
+        return self.filt.apply(input, F.DeviceArray(marker, info.chunk_shape, info.data_type),
+                               output, ctx=ctx)
+
+
+def reconstruction(input_path, output_path, marker_path=None, method: str = "dilation",
+                   connectivity: int = 1, mode: Optional[str] = None, h=None,
+                   data_type: Optional[str] = None, device: int = 0, nthreads: int = 0,
+                   encoding=None) -> dict:
+    """zarrs_filter reconstruction INPUT OUTPUT (--marker PATH | --fill-holes | --h-maxima H |
+    --h-minima H) [--method dilation|erosion] [--connectivity C]: morphological reconstruction
+    under the mask INPUT (filter.Reconstruction) of the marker array at `marker_path` (same shape
+    and data type; any chunk grid and codecs), or of a marker made from the mask (`mode`
+    "fill_holes", "h_maxima", "h_minima"). The output has the input's data type and fill value. The
+    result at an element may depend on every chunk, so the arrays are read into device memory,
+    reconstructed there and the result written once; there is no store -> store path, and arrays
+    that do not fit 80 % of the free device memory fail with ZT_ERR_OUT_OF_MEMORY before anything
+    is read. Returns the run stats and "rounds"."""
+    import time
+    from . import filter as F
+    from .device_io import _read_pieces
+    t0 = time.perf_counter()
+    info = open_array(input_path)
+    mode = mode or "marker"
+    filt = F.Reconstruction(method, connectivity, mode, h)
+    if (filt.mode == "marker") != (marker_path is not None):
+        raise _abi.InvalidParameters(
+            _abi.ERR_INVALID_PARAMETERS,
+            "reconstruction: mode marker needs a marker array" if marker_path is None else
+            f"reconstruction: {filt.mode} makes its marker from the mask; no marker array is given")
+    dt, enc = reconstruction_output(input_path, data_type, encoding)
+    step = filt
+    if marker_path is not None:
+        minfo = open_array(marker_path)
+        filt.is_compatible(info.data_type, minfo.data_type)
+        if tuple(minfo.shape) != tuple(info.shape):
+            raise _abi.InvalidParameters(
+                _abi.ERR_INVALID_PARAMETERS,
+                f"Array shapes do not match: {list(info.shape)} vs {list(minfo.shape)}")
+        step = MarkerStep(filt, marker_path, device, nthreads)
+    else:
+        filt.is_compatible(info.data_type)
+    filt.check_connectivity(info.ndim)
+    no_fallback = ("reconstruction works on the whole array in device memory (the result at an "
+                   "element may depend on every chunk): there is no store -> store path to fall "
+                   "back to")
+    shape = [int(s) for s in info.shape]
+    if marker_path is not None and all(s > 0 for s in shape):
+        # the pinned pieces of the marker's read, before anything is read (the mask's pieces and
+        # the output's rows are _whole_array_step's)
+        esz = NUMPY[minfo.data_type]().itemsize
+        pieces = _read_pieces([0] * minfo.ndim, shape, minfo.chunk_shape, esz)
+        plane2 = int(np.prod(shape[2:])) if minfo.ndim > 2 else 1
+        host_need = min(3, len(pieces)) * esz * max(
+            (b - a) * (yb - ya) * plane2 for a, b, ya, yb in pieces)
+        host_budget = host_available_bytes() // 10 * 8
+        if host_need > host_budget:
+            raise _abi.FilterError(
+                _abi.ERR_OUT_OF_MEMORY,
+                "There is not enough available memory to process the array: its pinned host "
+                f"buffers need {host_need} bytes and 80 % of the available memory is "
+                f"{host_budget}; {no_fallback}")
+    st, rounds = _whole_array_step(
+        input_path, output_path, info, step, dt, enc, device, nthreads, t0,
+        "mask, marker, output and one working array" if marker_path is not None else
+        "mask, output and one working array", no_fallback)
+    st["rounds"] = int(rounds)
+    return st
+
+
 def label_statistics(labels_path, intensity_path=None, n_labels: Optional[int] = None,
                      device: int = 0, nthreads: int = 0) -> dict:
     """zarrs_info PATH label-statistics [--intensity PATH] [--n-labels K]: the per-label count,

@@ -1,7 +1,8 @@
 """``zarrs_filter`` for the on-path filters (guided_filter, downsample, gaussian,
 summed_area_table, the rank filters median, minimum, maximum, the per-element reencode, crop,
 rescale, clamp, equal, replace_value, the two-array arithmetic and the whole-array
-connected_components, distance_transform and label_size_filter) over Zarr V3 stores.
+connected_components, distance_transform, label_size_filter and reconstruction) over Zarr V3
+stores.
 
 Mirrors src/bin/zarrs_filter.rs (LDeakin/zarrs_tools 0.7.2) for the filters this framework
 accelerates:
@@ -24,7 +25,10 @@ accelerates:
                                         | distance-transform IN OUT [--spacing S[,S...]]
                                               [--squared] [--data-type T]
                                         | label-size-filter IN OUT [--min-size N] [--max-size N]
-                                              [--no-relabel] [--data-type T]]
+                                              [--no-relabel] [--data-type T]
+                                        | reconstruction IN OUT (--marker PATH | --fill-holes
+                                              | --h-maxima H | --h-minima H)
+                                              [--method dilation|erosion] [--connectivity C]]
 
 * subcommand arguments as GuidedFilterArguments (guided_filter.rs:25-33),
   DownsampleArguments (downsample.rs:20-33, STRIDE comma delimited) and GaussianArguments
@@ -59,14 +63,25 @@ accelerates:
   1 .. K' in increasing order of their old value unless --no-relabel; OUT has IN's type and fill
   value 0 unless --data-type names another integer type, and the step fails, writing nothing,
   when the largest output label does not fit it or an element is negative; the step logs K';
+  reconstruction (an extension: the reference has none) reconstructs a marker
+  under the mask IN: by dilation the least J >= min(marker, mask) with J[p] = min(max(J over p and
+  its neighbours), mask[p]), by erosion the same with the order reversed (--method, with --marker
+  only; default dilation), neighbours as connected-components' (--connectivity, default 1);
+  --marker PATH is a second array of IN's shape and data type, of any chunk grid and codecs;
+  --fill-holes (by erosion, the marker is the mask on the array's border and the type's greatest
+  value elsewhere: on a mask of background it fills the holes), --h-maxima H (by dilation, the
+  marker is IN - H) and --h-minima H (by erosion, IN + H), H a finite number > 0, make the marker
+  from the mask on the device; exactly one of the four is given; OUT has IN's data type and fill
+  value; the step logs its rounds;
 * a JSON run config is a list of {"filter": "guided_filter" | "downsample" | "gaussian" |
   "summed_area_table" | "median" | "minimum" | "maximum" | "reencode" | "crop" | "rescale" |
   "clamp" | "equal" | "replace_value" | "arithmetic" | "connected_components" |
-  "distance_transform" | "label_size_filter", "input", "output", ...args (kernel_half_size; offset, shape, multiply, add, add_first, min, max, value, replace
+  "distance_transform" | "label_size_filter" | "reconstruction", "input", "output", ...args (kernel_half_size; offset, shape, multiply, add, add_first, min, max, value, replace
   for the per-element filters; connectivity for connected_components; spacing, squared for
-  distance_transform; min_size, max_size, relabel for label_size_filter; operator, other for
-  arithmetic, whose "other" is a path or the
-  "$name" of a temporary that an earlier step wrote), "data_type"}, with "$name" meaning a named
+  distance_transform; min_size, max_size, relabel for label_size_filter; marker, mode, h, method,
+  connectivity for reconstruction ("mode" one of marker, fill_holes, h_maxima, h_minima: marker
+  when a "marker" is given); operator, other for arithmetic; "other" and "marker" are a path or
+  the "$name" of a temporary that an earlier step wrote), "data_type"}, with "$name" meaning a named
   temporary array under --tmp and an omitted input meaning the previous filter's output (zarrs_filter.rs:106-138,
   :338-381);
 * a chain of steps linked only through temporaries (a "$name" or implicit output read by the
@@ -82,7 +97,10 @@ accelerates:
   a connected_components step may be part of such a chain (equal -> connected_components labels
   a mask that never touches the store), and the chain's budget then counts its two index arrays;
   so may a distance_transform step (equal -> distance_transform -> clamp erodes a mask by a ball),
-  whose work arrays and stacks the budget counts in the same way;
+  whose work arrays and stacks the budget counts in the same way; so may a reconstruction step
+  that makes its marker from the mask (equal -> reconstruction(fill_holes) ->
+  connected_components -> label_size_filter is one chain); one with a marker array is never part
+  of a chain, and a temporary that a later step reads as its "marker" is written to the store;
 * every filter takes the reencoding arguments (ZarrReencodingArgs, lib.rs:274-377: -d/--data-type,
   -f/--fill-value, --separator, -c/--chunk-shape, -s/--shard-shape, --array-to-array-codecs,
   --array-to-bytes-codec, --bytes-to-bytes-codecs, --dimension-names, --attributes,
@@ -97,7 +115,7 @@ accelerates:
 gradient_magnitude is rejected with FilterError::Other: it runs from the library only
 (DESIGN.md §1). A summed-area table's chunk rows each need the previous row's last plane, so with
 --gpus > 1 that step runs in one process on the first device (`rows_splittable`); so do
-connected_components, distance_transform and label_size_filter, whose unit of work is the whole array: it is read
+connected_components, distance_transform, label_size_filter and reconstruction, whose unit of work is the whole array: it is read
 into device memory, processed and written once, and fails with the out-of-memory error when it
 does not fit (there is no store -> store path for them). The other
 filters' rows, the per-element ones included, are split over the processes. `--chunk-limit N`
@@ -128,7 +146,8 @@ POINTWISE = ("reencode", "crop", "rescale", "clamp", "equal", "replace_value")
 RANK = ("median", "minimum", "maximum")
 BINARY = ("arithmetic",)  # two arrays in: "input" and "other"
 # no chunk rows at all: the array is the unit of work
-WHOLE_ARRAY = ("connected_components", "distance_transform", "label_size_filter")
+WHOLE_ARRAY = ("connected_components", "distance_transform", "label_size_filter",
+               "reconstruction")
 ON_PATH = ("guided_filter", "downsample", "gaussian", "summed_area_table") + RANK + POINTWISE + \
     BINARY + WHOLE_ARRAY
 
@@ -336,6 +355,26 @@ def build_parser() -> argparse.ArgumentParser:
                      help="kept labels keep their values (default: renumbered 1 .. K' in "
                           "increasing order)")
     _add_reencode_args(lsf)
+    rc = sub.add_parser("reconstruction",
+                        help="Morphological reconstruction of a marker under the mask IN.")
+    rc.add_argument("input")
+    rc.add_argument("output")
+    how = rc.add_mutually_exclusive_group(required=True)
+    how.add_argument("--marker", default=None,
+                     help="the marker: a second array of IN's shape and data type")
+    how.add_argument("--fill-holes", action="store_true",
+                     help="by erosion from the array's border: fills the holes of a mask of "
+                          "background")
+    how.add_argument("--h-maxima", type=float, default=None, metavar="H",
+                     help="by dilation of IN - H: suppresses maxima lower than H")
+    how.add_argument("--h-minima", type=float, default=None, metavar="H",
+                     help="by erosion of IN + H: suppresses minima shallower than H")
+    rc.add_argument("--method", choices=["dilation", "erosion"], default=None,
+                    help="with --marker only (default dilation)")
+    rc.add_argument("--connectivity", type=int, default=1,
+                    help="neighbours differ on at most this many axes (1: faces, the default; "
+                         "the rank: the full neighbourhood)")
+    _add_reencode_args(rc)
     return ap
 
 
@@ -385,6 +424,25 @@ def _steps_from_cli(a) -> list:
                  "min_size": a.min_size, "max_size": a.max_size, "relabel": not a.no_relabel,
                  "data_type": a.data_type, "chunk_limit": a.filter_chunk_limit,
                  **_reencode_of(a)}]
+    if a.filter == "reconstruction":
+        if a.method is not None and a.marker is None:
+            raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS,
+                                         "reconstruction: --method is only valid with --marker")
+        mode, h = "marker", None
+        if a.fill_holes:
+            mode = "fill_holes"
+        elif a.h_maxima is not None:
+            mode, h = "h_maxima", a.h_maxima
+        elif a.h_minima is not None:
+            mode, h = "h_minima", a.h_minima
+        step = {"filter": "reconstruction", "input": a.input, "output": a.output, "mode": mode,
+                "connectivity": a.connectivity, "data_type": a.data_type,
+                "chunk_limit": a.filter_chunk_limit, **_reencode_of(a)}
+        if a.marker is not None:
+            step.update(marker=a.marker, method=a.method or "dilation")
+        if h is not None:
+            step["h"] = h
+        return [step]
     return []
 
 
@@ -396,16 +454,19 @@ def plan_chains(steps: list) -> list:
     """Maximal runs [i, j] of steps (j > i) where every step before j hands its output to the next
     step only: the output is a temporary (a "$name", or omitted) and the next step reads it (its
     input is that "$name", or omitted = the previous output), and no other step names it, as
-    its input, output or (arithmetic) "other". An arithmetic step is never part of a chain."""
+    its input, output, (arithmetic) "other" or (reconstruction) "marker". An arithmetic step and
+    a reconstruction step with a marker array are never part of a chain."""
     refs: dict = {}
     for st in steps:
-        for key in ("input", "output", "other"):
+        for key in ("input", "output", "other", "marker"):
             v = st.get(key)
             if isinstance(v, str) and v.startswith("$"):
                 refs[v] = refs.get(v, 0) + 1
 
     def linked(k):
         if steps[k].get("filter") in BINARY or steps[k + 1].get("filter") in BINARY:
+            return False
+        if steps[k].get("marker") is not None or steps[k + 1].get("marker") is not None:
             return False
         out, nxt = steps[k].get("output"), steps[k + 1].get("input")
         if not _is_temp(out):
@@ -515,6 +576,37 @@ def connectivity_of(step: dict) -> int:
                                      "integer") from None
 
 
+def reconstruction_of(step: dict):
+    """(Reconstruction, marker) of a run-config step: "marker" a path or the "$name" of an earlier
+    step's output (then "mode" is marker, or omitted), or "mode" one of fill_holes, h_maxima,
+    h_minima with "h" for the last two; "method" dilation (default) or erosion, with a marker
+    only; "connectivity" an integer (default 1)."""
+    from . import filter as F
+    marker = step.get("marker")
+    mode = step.get("mode") or ("marker" if marker is not None else None)
+    if mode is None:
+        raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS,
+                                     "reconstruction needs a marker or a mode (fill_holes, "
+                                     "h_maxima, h_minima)")
+    mode = str(mode).replace("-", "_")
+    if (mode == "marker") != (marker is not None):
+        raise _abi.InvalidParameters(
+            _abi.ERR_INVALID_PARAMETERS,
+            "reconstruction: mode marker needs a marker" if marker is None else
+            f"reconstruction: {mode} makes its marker from the mask; no marker is given")
+    if step.get("method") is not None and marker is None:
+        raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS,
+                                     "reconstruction: a method is only valid with a marker")
+    c = step.get("connectivity")
+    try:
+        c = 1 if c is None else int(c)
+    except (TypeError, ValueError):
+        raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS,
+                                     f"reconstruction: connectivity {c!r} is not an "
+                                     "integer") from None
+    return F.Reconstruction(step.get("method") or "dilation", c, mode, step.get("h")), marker
+
+
 def distance_transform_of(step: dict):
     """The DistanceTransform of a run-config step: "spacing" a list (or a comma delimited string)
     of integers >= 1, default all 1; "squared" a boolean, default false."""
@@ -565,6 +657,15 @@ def _step_params(step, info):
         f.is_compatible(info.data_type, dt)
         return f, tuple(info.shape), dt
     dt = step.get("data_type") or (encoding_of(step) or {}).get("data_type") or info.data_type
+    if name == "reconstruction":
+        f, _marker = reconstruction_of(step)
+        if dt != info.data_type:
+            raise _abi.UnsupportedDataType(
+                _abi.ERR_UNSUPPORTED_DATA_TYPE,
+                f"reconstruction: the output has the input's data type {info.data_type}, not {dt}")
+        f.is_compatible(info.data_type)
+        f.check_connectivity(info.ndim)
+        return f, tuple(info.shape), dt
     if name == "guided_filter":
         if "epsilon" not in step or "radius" not in step:
             raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS,
@@ -717,6 +818,8 @@ def run_device_chain(steps: list, paths: list, device: int = 0, nthreads: int = 
         if names in ("connected_components", "label_size_filter"):  # the steps with a count
             components = int(ret)
             log(f"   {components} components")
+        if names == "reconstruction":
+            log(f"   {int(ret)} rounds")
         if names in WHOLE_ARRAY:
             ctx.release_scratch()  # whole-array scratch: not held through the rest of the chain
         for k in range(i, j + 1):
@@ -731,6 +834,8 @@ def run_device_chain(steps: list, paths: list, device: int = 0, nthreads: int = 
                     j if not carrier else list(range(i, j + 1)))
             if components is not None:
                 st["components"] = components
+            if names == "reconstruction":
+                st["rounds"] = int(ret)
             results.append(st)
         x, x_dt, x_chunk = y, out_info.data_type, out_info.chunk_shape
     t2 = time.perf_counter()
@@ -948,6 +1053,18 @@ def run(steps: list, exists: str = "erase", tmp: str | None = None,
             params = {"min_size": f.min_size, "max_size": f.max_size, "relabel": f.relabel}
             log(f"{i}: label_size_filter min_size={f.min_size} max_size={f.max_size} "
                 f"relabel={f.relabel} {src} ({info.data_type} {list(info.shape)}) -> {dst}")
+        elif name == "reconstruction":
+            marker = reconstruction_of(step)[1]
+            if isinstance(marker, str) and marker.startswith("$"):
+                marker = temps[marker]  # written by an earlier step (checked before the run)
+            params = {"marker": None if marker is None else str(marker), "mode": f.mode,
+                      "method": f.method, "connectivity": f.connectivity,
+                      "h": f.h if f.mode in ("h_maxima", "h_minima") else None}
+            log(f"{i}: reconstruction mode={f.mode} method={f.method} "
+                f"connectivity={f.connectivity}"
+                + (f" h={f.h}" if params["h"] is not None else "")
+                + f" {src} ({info.data_type} {list(info.shape)})"
+                + (f" marker {marker}" if marker is not None else "") + f" -> {dst}")
         else:
             params = {"stride": list(f.stride), "discrete": bool(step.get("discrete", False))}
             log(f"{i}: downsample stride={params['stride']} discrete={params['discrete']} "
@@ -967,6 +1084,11 @@ def run(steps: list, exists: str = "erase", tmp: str | None = None,
                 return S.label_size_filter(src, dst, params["min_size"], params["max_size"],
                                            params["relabel"], data_type=params["data_type"],
                                            device=dev, encoding=enc)
+            if name == "reconstruction":
+                return S.reconstruction(src, dst, params["marker"],
+                                        params["method"] if params["marker"] else "dilation",
+                                        params["connectivity"], params["mode"], params["h"],
+                                        data_type=params["data_type"], device=dev, encoding=enc)
             return S.summed_area_table(src, dst, data_type=params["data_type"], device=dev,
                                        encoding=enc, chunk_limit=limit)
 
@@ -1005,6 +1127,8 @@ def run(steps: list, exists: str = "erase", tmp: str | None = None,
                               chunk_limit=limit)
         if "components" in st:
             log(f"   {st['components']} components")
+        if "rounds" in st:
+            log(f"   {st['rounds']} rounds")
         out = S.open_array(dst)
         log(f"   -> {out.data_type} {list(out.shape)} in {st['wall_s']:.2f}s "
             f"(rw:{st['decode_s']:.2f}/{st['encode_s']:.2f} p:{st['kernel_s']:.3f})")
@@ -1026,6 +1150,12 @@ def run(steps: list, exists: str = "erase", tmp: str | None = None,
                 raise _abi.InvalidParameters(
                     _abi.ERR_INVALID_PARAMETERS,
                     f"arithmetic: other {other} is not the output of an earlier step")
+        if step.get("filter") == "reconstruction":
+            marker = reconstruction_of(step)[1]
+            if isinstance(marker, str) and marker.startswith("$") and marker not in written:
+                raise _abi.InvalidParameters(
+                    _abi.ERR_INVALID_PARAMETERS,
+                    f"reconstruction: marker {marker} is not the output of an earlier step")
         out = step.get("output")
         if isinstance(out, str) and out.startswith("$"):
             written.add(out)
@@ -1085,7 +1215,11 @@ def main(argv=None) -> int:
         if isinstance(steps, dict):
             steps = [steps]
     else:
-        steps = _steps_from_cli(a)
+        try:
+            steps = _steps_from_cli(a)
+        except _abi.FilterError as e:  # an option conflict that argparse cannot express
+            print(f"Error: {e}", file=sys.stderr)
+            return 1
     if not steps:
         build_parser().print_help()
         return 2
