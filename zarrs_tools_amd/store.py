@@ -472,16 +472,50 @@ def device_available_bytes(device: int = 0) -> int:
     return int(torch.cuda.mem_get_info(device)[0])
 
 
-def connected_components_output(data_type: Optional[str] = None, encoding=None):
-    """(output data type, encoding) of a labelling's output array: an explicit data type
-    (`data_type` or the encoding's) wins, else uint32; the fill value is 0 unless given."""
-    enc = dict(encoding) if isinstance(encoding, dict) else (
+def _encoding_dict(encoding) -> dict:
+    """Reencoding arguments (a dict, its JSON, or None) as a dict of the caller's own."""
+    return dict(encoding) if isinstance(encoding, dict) else (
         json.loads(encoding) if encoding else {})
-    dt = enc.get("data_type") or data_type or "uint32"
+
+
+def _typed_output(default: str, data_type: Optional[str], encoding):
+    """(output data type, encoding) of an output array whose filter sets its type: an explicit
+    data type (`data_type` or the encoding's) wins, else `default`; the fill value is 0 unless
+    given."""
+    enc = _encoding_dict(encoding)
+    dt = enc.get("data_type") or data_type or default
     enc["data_type"] = dt
     if enc.get("fill_value") is None:
         enc["fill_value"] = 0
     return dt, enc
+
+
+def _pinned_read_bytes(shape, chunk_shape, esz: int) -> int:
+    """The pinned host bytes of reading an array of `shape` (no axis empty) into device memory:
+    device_io.read_to_device holds up to three buffers of the largest of its pieces."""
+    from .device_io import _read_pieces
+    pieces = _read_pieces([0] * len(shape), shape, chunk_shape, esz)
+    plane2 = int(np.prod(shape[2:])) if len(shape) > 2 else 1
+    return min(3, len(pieces)) * esz * max(
+        (b - a) * (yb - ya) * plane2 for a, b, ya, yb in pieces)
+
+
+PINNED_BUFFERS_NEED = "its pinned host buffers need {} bytes"
+
+
+def _not_enough_memory(need: int, budget: int, needs: str, why: str):
+    """The error of an array that does not fit 80 % of the available memory: `needs` says what
+    needs the `need` bytes (its {} is their place), `why` what the step cannot do instead."""
+    raise _abi.FilterError(
+        _abi.ERR_OUT_OF_MEMORY,
+        f"There is not enough available memory to process the array: {needs.format(need)} and "
+        f"80 % of the available memory is {budget}; {why}")
+
+
+def connected_components_output(data_type: Optional[str] = None, encoding=None):
+    """(output data type, encoding) of a labelling's output array: uint32 unless given
+    (_typed_output)."""
+    return _typed_output("uint32", data_type, encoding)
 
 
 def connected_components(input_path, output_path, connectivity: int = 1,
@@ -519,7 +553,7 @@ def _whole_array_step(input_path, output_path, info, filt, dt, enc, device, nthr
     stats, what `filt.apply` returned)."""
     import time
     from . import filter as F
-    from .device_io import _read_pieces, _row_spans, read_to_device, write_from_device
+    from .device_io import _row_spans, read_to_device, write_from_device
     for name in ("zarr.json", PENDING_METADATA):  # the output is not finished until the end
         try:
             os.remove(os.path.join(output_path, name))
@@ -532,28 +566,18 @@ def _whole_array_step(input_path, output_path, info, filt, dt, enc, device, nthr
     need = filt.memory(info.data_type, dt, shape)
     budget = device_available_bytes(device) // 10 * 8
     if need > budget:
-        raise _abi.FilterError(
-            _abi.ERR_OUT_OF_MEMORY,
-            "There is not enough available memory to process the array: it needs "
-            f"{need} bytes of device memory ({terms}) and 80 % of "
-            f"the available memory is {budget}; {no_fallback}")
+        _not_enough_memory(need, budget, f"it needs {{}} bytes of device memory ({terms})",
+                           no_fallback)
     host_need = 0
     if all(s > 0 for s in shape):
-        pieces = _read_pieces([0] * info.ndim, shape, info.chunk_shape, in_esz)
-        plane2 = int(np.prod(shape[2:])) if info.ndim > 2 else 1
-        piece_b = max((b - a) * (yb - ya) * plane2 for a, b, ya, yb in pieces) * in_esz
         out_chunk0 = int((enc.get("shard_shape") or enc.get("chunk_shape") or info.chunk_shape)[0])
         rows = max(b - a for a, b in _row_spans(0, shape[0], out_chunk0))
         row_b = rows * int(np.prod(shape[1:])) * out_esz
-        host_need = max(min(3, len(pieces)) * piece_b,
+        host_need = max(_pinned_read_bytes(shape, info.chunk_shape, in_esz),
                         min(2, -(-shape[0] // out_chunk0)) * row_b)
     host_budget = host_available_bytes() // 10 * 8
     if host_need > host_budget:
-        raise _abi.FilterError(
-            _abi.ERR_OUT_OF_MEMORY,
-            "There is not enough available memory to process the array: its pinned host "
-            f"buffers need {host_need} bytes and 80 % of the available memory is {host_budget}; "
-            f"{no_fallback}")
+        _not_enough_memory(host_need, host_budget, PINNED_BUFFERS_NEED, no_fallback)
     create_output(input_path, output_path, dt, None, enc)
     hold_metadata(output_path)  # "not finished" until the chunks are written
     out_info = open_array(output_path)
@@ -586,17 +610,10 @@ def _whole_array_step(input_path, output_path, info, filt, dt, enc, device, nthr
 
 def distance_transform_output(squared: bool = False, data_type: Optional[str] = None,
                               encoding=None):
-    """(output data type, encoding) of a distance transform's output array: an explicit data
-    type (`data_type` or the encoding's) wins, else float32, or uint32 for squared distances; the
-    fill value is 0 unless given."""
+    """(output data type, encoding) of a distance transform's output array: float32, or uint32
+    for squared distances, unless given (_typed_output)."""
     from .filter import distance_transform_default_type
-    enc = dict(encoding) if isinstance(encoding, dict) else (
-        json.loads(encoding) if encoding else {})
-    dt = enc.get("data_type") or data_type or distance_transform_default_type(squared)
-    enc["data_type"] = dt
-    if enc.get("fill_value") is None:
-        enc["fill_value"] = 0
-    return dt, enc
+    return _typed_output(distance_transform_default_type(squared), data_type, encoding)
 
 
 def distance_transform(input_path, output_path, spacing=None, squared: bool = False,
@@ -627,15 +644,9 @@ def distance_transform(input_path, output_path, spacing=None, squared: bool = Fa
 
 def label_size_filter_output(input_data_type: str, data_type: Optional[str] = None,
                              encoding=None):
-    """(output data type, encoding) of a size filter's output array: an explicit data type
-    (`data_type` or the encoding's) wins, else the input's; the fill value is 0 unless given."""
-    enc = dict(encoding) if isinstance(encoding, dict) else (
-        json.loads(encoding) if encoding else {})
-    dt = enc.get("data_type") or data_type or input_data_type
-    enc["data_type"] = dt
-    if enc.get("fill_value") is None:
-        enc["fill_value"] = 0
-    return dt, enc
+    """(output data type, encoding) of a size filter's output array: the input's type unless
+    given (_typed_output)."""
+    return _typed_output(input_data_type, data_type, encoding)
 
 
 class SizeFilterStep:
@@ -691,8 +702,7 @@ def label_size_filter(input_path, output_path, min_size: int = 1, max_size: Opti
 def reconstruction_output(input_path, data_type: Optional[str] = None, encoding=None):
     """(output data type, encoding) of a reconstruction's output array: the input's type (an
     explicit other type is UnsupportedDataType) and, unless given, the input's fill value."""
-    enc = dict(encoding) if isinstance(encoding, dict) else (
-        json.loads(encoding) if encoding else {})
+    enc = _encoding_dict(encoding)
     info = open_array(input_path)
     dt = enc.get("data_type") or data_type or info.data_type
     if dt != info.data_type:
@@ -738,7 +748,6 @@ def reconstruction(input_path, output_path, marker_path=None, method: str = "dil
     is read. Returns the run stats and "rounds"."""
     import time
     from . import filter as F
-    from .device_io import _read_pieces
     t0 = time.perf_counter()
     info = open_array(input_path)
     mode = mode or "marker"
@@ -768,18 +777,11 @@ def reconstruction(input_path, output_path, marker_path=None, method: str = "dil
     if marker_path is not None and all(s > 0 for s in shape):
         # the pinned pieces of the marker's read, before anything is read (the mask's pieces and
         # the output's rows are _whole_array_step's)
-        esz = NUMPY[minfo.data_type]().itemsize
-        pieces = _read_pieces([0] * minfo.ndim, shape, minfo.chunk_shape, esz)
-        plane2 = int(np.prod(shape[2:])) if minfo.ndim > 2 else 1
-        host_need = min(3, len(pieces)) * esz * max(
-            (b - a) * (yb - ya) * plane2 for a, b, ya, yb in pieces)
+        host_need = _pinned_read_bytes(shape, minfo.chunk_shape,
+                                       NUMPY[minfo.data_type]().itemsize)
         host_budget = host_available_bytes() // 10 * 8
         if host_need > host_budget:
-            raise _abi.FilterError(
-                _abi.ERR_OUT_OF_MEMORY,
-                "There is not enough available memory to process the array: its pinned host "
-                f"buffers need {host_need} bytes and 80 % of the available memory is "
-                f"{host_budget}; {no_fallback}")
+            _not_enough_memory(host_need, host_budget, PINNED_BUFFERS_NEED, no_fallback)
     st, rounds = _whole_array_step(
         input_path, output_path, info, step, dt, enc, device, nthreads, t0,
         "mask, marker, output and one working array" if marker_path is not None else
@@ -815,12 +817,9 @@ def label_statistics(labels_path, intensity_path=None, n_labels: Optional[int] =
     budget = device_available_bytes(device) // 10 * 8
 
     def refuse(need, k, hint):
-        raise _abi.FilterError(
-            _abi.ERR_OUT_OF_MEMORY,
-            "There is not enough available memory to process the array: it needs "
-            f"{need} bytes of device memory (labels, intensities and the state of {k} "
-            f"labels) and 80 % of the available memory is {budget}; label_statistics reduces "
-            f"the whole array in device memory{hint}")
+        _not_enough_memory(need, budget, "it needs {} bytes of device memory (labels, "
+                           f"intensities and the state of {k} labels)",
+                           f"label_statistics reduces the whole array in device memory{hint}")
 
     # budget, before anything is read: the arrays, and the state when n_labels says how large it
     # is; with n_labels=None the state is budgeted once the range reduction has given K
@@ -850,8 +849,7 @@ def pointwise_output(filt, input_data_type: str, data_type: Optional[str] = None
     output_array_builder decides it (filter_traits.rs:47-82): an explicit data type (`data_type`
     or the encoding's) wins; else the filter's own (Equal::output_data_type: bool with fill value
     false, equal.rs:121-123), which also sets the fill value; else the input's."""
-    enc = dict(encoding) if isinstance(encoding, dict) else (
-        json.loads(encoding) if encoding else {})
+    enc = _encoding_dict(encoding)
     dt = enc.get("data_type") or data_type
     if dt is None:
         auto = filt.output_data_type(input_data_type)

@@ -1,34 +1,15 @@
-"""``zarrs_filter`` for the on-path filters (guided_filter, downsample, gaussian,
-summed_area_table, the rank filters median, minimum, maximum, the per-element reencode, crop,
-rescale, clamp, equal, replace_value, the two-array arithmetic and the whole-array
-connected_components, distance_transform, label_size_filter and reconstruction) over Zarr V3
-stores.
+"""``zarrs_filter`` for the on-path filters over Zarr V3 stores. What the tool knows about a kind
+of step is one record of STEP_KINDS (below): the sub-parser, the run-config keys, the output
+array's type, the call into `store` and how the step may run are all read from it.
 
 Mirrors src/bin/zarrs_filter.rs (LDeakin/zarrs_tools 0.7.2) for the filters this framework
 accelerates:
 
     python -m zarrs_tools_amd.zarrs_filter [--exists erase|exit] [--tmp DIR] [--chunk-limit N]
-        [--device D] [RUN_CONFIG.json] [guided-filter IN OUT EPSILON RADIUS [--data-type T]
-                                        | downsample IN OUT STRIDE [--discrete] [--data-type T]
-                                        | gaussian IN OUT SIGMA KERNEL_HALF_SIZE [--data-type T]
-                                        | summed-area-table IN OUT [--data-type T]
-                                        | median IN OUT KERNEL_HALF_SIZE [--data-type T]
-                                        | minimum IN OUT KERNEL_HALF_SIZE [--data-type T]
-                                        | maximum IN OUT KERNEL_HALF_SIZE [--data-type T]
-                                        | reencode IN OUT | crop IN OUT OFFSET SHAPE
-                                        | rescale IN OUT MULTIPLY ADD [--add-first]
-                                        | clamp IN OUT MIN MAX | equal IN OUT VALUE
-                                        | replace-value IN OUT VALUE REPLACE
-                                        | arithmetic IN OUT OPERATOR OTHER [--data-type T]
-                                        | connected-components IN OUT [--connectivity C]
-                                              [--data-type T]
-                                        | distance-transform IN OUT [--spacing S[,S...]]
-                                              [--squared] [--data-type T]
-                                        | label-size-filter IN OUT [--min-size N] [--max-size N]
-                                              [--no-relabel] [--data-type T]
-                                        | reconstruction IN OUT (--marker PATH | --fill-holes
-                                              | --h-maxima H | --h-minima H)
-                                              [--method dilation|erosion] [--connectivity C]]
+        [--device D] [RUN_CONFIG.json] [SUBCOMMAND IN OUT ARGS... [--data-type T]]
+
+with one SUBCOMMAND per record, its name with hyphens (`--help` lists them, `SUBCOMMAND --help`
+its arguments).
 
 * subcommand arguments as GuidedFilterArguments (guided_filter.rs:25-33),
   DownsampleArguments (downsample.rs:20-33, STRIDE comma delimited) and GaussianArguments
@@ -73,11 +54,9 @@ accelerates:
   marker is IN - H) and --h-minima H (by erosion, IN + H), H a finite number > 0, make the marker
   from the mask on the device; exactly one of the four is given; OUT has IN's data type and fill
   value; the step logs its rounds;
-* a JSON run config is a list of {"filter": "guided_filter" | "downsample" | "gaussian" |
-  "summed_area_table" | "median" | "minimum" | "maximum" | "reencode" | "crop" | "rescale" |
-  "clamp" | "equal" | "replace_value" | "arithmetic" | "connected_components" |
-  "distance_transform" | "label_size_filter" | "reconstruction", "input", "output", ...args (kernel_half_size; offset, shape, multiply, add, add_first, min, max, value, replace
-  for the per-element filters; connectivity for connected_components; spacing, squared for
+* a JSON run config is a list of {"filter": a record's name, "input", "output", ...args
+  (kernel_half_size; offset, shape, multiply, add, add_first, min, max, value, replace for the
+  per-element filters; connectivity for connected_components; spacing, squared for
   distance_transform; min_size, max_size, relabel for label_size_filter; marker, mode, h, method,
   connectivity for reconstruction ("mode" one of marker, fill_holes, h_maxima, h_minima: marker
   when a "marker" is given); operator, other for arithmetic; "other" and "marker" are a path or
@@ -128,6 +107,8 @@ even one row fits.
 from __future__ import annotations
 
 import argparse
+import dataclasses
+import functools
 import json
 import os
 import re
@@ -139,26 +120,9 @@ import time
 import numpy as np
 
 from . import _abi
+from . import filter as F
 from . import store as S
 from .device_io import _read_pieces, _row_spans, read_to_device, write_from_device  # noqa: F401
-
-POINTWISE = ("reencode", "crop", "rescale", "clamp", "equal", "replace_value")
-RANK = ("median", "minimum", "maximum")
-BINARY = ("arithmetic",)  # two arrays in: "input" and "other"
-# no chunk rows at all: the array is the unit of work
-WHOLE_ARRAY = ("connected_components", "distance_transform", "label_size_filter",
-               "reconstruction")
-ON_PATH = ("guided_filter", "downsample", "gaussian", "summed_area_table") + RANK + POINTWISE + \
-    BINARY + WHOLE_ARRAY
-
-
-def rows_splittable(name: str) -> bool:
-    """Whether a store step's output chunk rows are independent, so that --gpus > 1 may split
-    them over processes. A summed-area table's rows are not: each row's axis-0 sum starts from
-    the previous row's last plane (summed_area_table.rs:69, :94-97). Nor are a labelling's or a
-    distance transform's: a connected component may span every chunk, and the nearest background
-    element may lie in any."""
-    return name != "summed_area_table" and name not in WHOLE_ARRAY
 
 
 def _parse_stride(s: str):
@@ -229,6 +193,498 @@ def encoding_of(step: dict) -> dict | None:
     return enc or None
 
 
+def _invalid(message: str):
+    return _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS, message)
+
+
+def _need(step: dict, *keys):
+    missing = [k for k in keys if step.get(k) is None]
+    if missing:
+        raise _invalid(f"{step.get('filter')} needs {', '.join(missing)}")
+    return [step[k] for k in keys]
+
+
+def _ints(v):
+    return _parse_stride(v) if isinstance(v, str) else [int(x) for x in v]
+
+
+def _integer(step: dict, key: str, default, message: str):
+    """The integer step[key], `default` when it is absent; InvalidParameters(message) else."""
+    try:
+        return default if step.get(key) is None else int(step[key])
+    except (TypeError, ValueError):
+        raise _invalid(message) from None
+
+
+# ---- what the records of STEP_KINDS (below) are made of, where it takes more than a line: the
+# sub-parser's own arguments, the filter object of a run-config step, the checks that need the
+# output type
+
+def _args_guided_filter(p):
+    p.add_argument("epsilon", type=float)
+    p.add_argument("radius", type=int)
+
+
+def _args_downsample(p):
+    p.add_argument("stride", type=_parse_stride)
+    p.add_argument("--discrete", action="store_true")
+
+
+def _args_gaussian(p):
+    p.add_argument("sigma", type=_parse_floats)
+    p.add_argument("kernel_half_size", type=_parse_stride)
+
+
+def _args_rank(p):
+    p.add_argument("kernel_half_size", type=_parse_stride)
+
+
+def _args_crop(p):
+    p.add_argument("offset", type=_parse_stride)
+    p.add_argument("shape", type=_parse_stride)
+
+
+def _args_rescale(p):
+    p.add_argument("multiply", type=float)
+    p.add_argument("add", type=float)
+    p.add_argument("--add-first", action="store_true",
+                   help="perform the addition before the multiplication")
+
+
+def _args_clamp(p):
+    p.add_argument("min", type=float)
+    p.add_argument("max", type=float)
+
+
+def _args_equal(p):
+    p.add_argument("value", type=_parse_fill_value)
+
+
+def _args_replace_value(p):
+    p.add_argument("value", type=_parse_fill_value)
+    p.add_argument("replace", type=_parse_fill_value)
+
+
+def _args_arithmetic(p):
+    p.add_argument("operator", choices=[o.replace("_", "-") for o in _abi.AR_OPERATORS])
+    p.add_argument("other")
+
+
+def _args_connectivity(p):
+    p.add_argument("--connectivity", type=int, default=1,
+                   help="neighbours differ on at most this many axes (1: faces, the default; "
+                        "the rank: the full neighbourhood)")
+
+
+def _args_distance_transform(p):
+    p.add_argument("--spacing", type=_parse_stride, default=None,
+                   help="the length of a step along each axis: comma delimited integers >= 1, "
+                        "one per axis (default: all 1)")
+    p.add_argument("--squared", action="store_true",
+                   help="store the squared distance (an exact integer; uint32 by default)")
+
+
+def _args_label_size_filter(p):
+    p.add_argument("--min-size", type=int, default=1,
+                   help="the fewest elements of a label that is kept (default 1)")
+    p.add_argument("--max-size", type=int, default=None,
+                   help="the most elements of a label that is kept (default: no bound)")
+    p.add_argument("--no-relabel", action="store_true",
+                   help="kept labels keep their values (default: renumbered 1 .. K' in "
+                        "increasing order)")
+
+
+def _args_reconstruction(p):
+    how = p.add_mutually_exclusive_group(required=True)
+    how.add_argument("--marker", default=None,
+                     help="the marker: a second array of IN's shape and data type")
+    how.add_argument("--fill-holes", action="store_true",
+                     help="by erosion from the array's border: fills the holes of a mask of "
+                          "background")
+    how.add_argument("--h-maxima", type=float, default=None, metavar="H",
+                     help="by dilation of IN - H: suppresses maxima lower than H")
+    how.add_argument("--h-minima", type=float, default=None, metavar="H",
+                     help="by erosion of IN + H: suppresses minima shallower than H")
+    p.add_argument("--method", choices=["dilation", "erosion"], default=None,
+                   help="with --marker only (default dilation)")
+    _args_connectivity(p)
+
+
+def _own_reconstruction(a):
+    """The step's own keys: (those before "data_type", those after the reencoding keys)."""
+    if a.method is not None and a.marker is None:
+        raise _invalid("reconstruction: --method is only valid with --marker")
+    mode, last = "marker", {}
+    if a.marker is not None:
+        last = {"marker": a.marker, "method": a.method or "dilation"}
+    elif a.fill_holes:
+        mode = "fill_holes"
+    elif a.h_maxima is not None:
+        mode, last = "h_maxima", {"h": a.h_maxima}
+    elif a.h_minima is not None:
+        mode, last = "h_minima", {"h": a.h_minima}
+    return {"mode": mode, "connectivity": a.connectivity}, last
+
+
+def _make_guided_filter(step, info):
+    if "epsilon" not in step or "radius" not in step:
+        raise _invalid("guided_filter needs epsilon and radius")
+    return F.GuidedFilter(float(step["epsilon"]), int(step["radius"]))
+
+
+def _make_downsample(step, info):
+    stride = step.get("stride")
+    stride = _parse_stride(stride) if isinstance(stride, str) else stride
+    if not stride or len(stride) != info.ndim:
+        raise _invalid("downsample stride must match the array rank")
+    return F.Downsample(stride, discrete=bool(step.get("discrete", False)))
+
+
+def _make_gaussian(step, info):
+    sigma, half = step.get("sigma"), step.get("kernel_half_size")
+    sigma = _parse_floats(sigma) if isinstance(sigma, str) else sigma
+    half = _parse_stride(half) if isinstance(half, str) else half
+    if not sigma or not half or len(sigma) != info.ndim or len(half) != info.ndim:
+        raise _invalid("gaussian sigma and kernel_half_size need one entry per axis")
+    return F.Gaussian(sigma, half)
+
+
+def _make_rank(step, info):
+    name, half = step["filter"], step.get("kernel_half_size")
+    if half is None:
+        raise _invalid(f"{name} needs kernel_half_size")
+    half = _ints(half)
+    F.check_rank_half(name, half, info.ndim)
+    return F.RankFilter(name, half)
+
+
+def pointwise_filter(step: dict):
+    """The per-element filter object of a run-config step (keys as the reference's *Arguments
+    structs: offset, shape; multiply, add, add_first; min, max; value; value, replace)."""
+    kind = STEP_KINDS.get(step.get("filter"))
+    if kind is None or kind.family != "pointwise":
+        raise _invalid(f"{step.get('filter')} is not a per-element filter")
+    return kind.make(step, None)
+
+
+def arithmetic_args(step: dict):
+    """(operator, other) of an arithmetic run-config step."""
+    missing = [k for k in ("operator", "other") if step.get(k) is None]
+    if missing:
+        raise _invalid(f"arithmetic needs {', '.join(missing)}")
+    F.arithmetic_operator(step["operator"])  # InvalidParameters for an unknown name
+    return str(step["operator"]).replace("-", "_"), step["other"]
+
+
+def connectivity_of(step: dict, name: str = "connected_components") -> int:
+    """The connectivity of a run-config step of the filter `name` (default 1: faces)."""
+    return _integer(step, "connectivity", 1,
+                    f"{name}: connectivity {step.get('connectivity')!r} is not an integer")
+
+
+def distance_transform_of(step: dict, info=None):
+    """The DistanceTransform of a run-config step: "spacing" a list (or a comma delimited string)
+    of integers >= 1, default all 1; "squared" a boolean, default false."""
+    sp = step.get("spacing")
+    if isinstance(sp, str):
+        sp = [x.strip() for x in sp.split(",") if x.strip()]
+        try:
+            sp = [int(x) for x in sp]
+        except ValueError:
+            raise _invalid(f"distance_transform: spacing {step['spacing']!r} is not a list of "
+                           "integers") from None
+    elif sp is not None and not isinstance(sp, (list, tuple)):
+        sp = [sp]
+    return F.DistanceTransform(sp, bool(step.get("squared", False)))
+
+
+def label_size_filter_of(step: dict, info=None):
+    """The size filter of a run-config step: "min_size" (default 1) and "max_size" (default
+    none) integers, "relabel" a boolean (default true)."""
+    message = "label_size_filter: min_size and max_size are integers"
+    mn, mx = _integer(step, "min_size", 1, message), _integer(step, "max_size", None, message)
+    relabel = step.get("relabel")
+    return S.SizeFilterStep(F.LabelSizeFilter(mn, mx, True if relabel is None else bool(relabel)))
+
+
+def reconstruction_of(step: dict):
+    """(Reconstruction, marker) of a run-config step: "marker" a path or the "$name" of an earlier
+    step's output (then "mode" is marker, or omitted), or "mode" one of fill_holes, h_maxima,
+    h_minima with "h" for the last two; "method" dilation (default) or erosion, with a marker
+    only; "connectivity" an integer (default 1)."""
+    marker = step.get("marker")
+    mode = step.get("mode") or ("marker" if marker is not None else None)
+    if mode is None:
+        raise _invalid("reconstruction needs a marker or a mode (fill_holes, h_maxima, "
+                       "h_minima)")
+    mode = str(mode).replace("-", "_")
+    if (mode == "marker") != (marker is not None):
+        raise _invalid(
+            "reconstruction: mode marker needs a marker" if marker is None else
+            f"reconstruction: {mode} makes its marker from the mask; no marker is given")
+    if step.get("method") is not None and marker is None:
+        raise _invalid("reconstruction: a method is only valid with a marker")
+    c = connectivity_of(step, "reconstruction")
+    return F.Reconstruction(step.get("method") or "dilation", c, mode, step.get("h")), marker
+
+
+def _check_pointwise(f, info, dt):
+    f.is_compatible(info.data_type, dt)
+    f.op(info.data_type, dt)  # value / replace must fit the types
+
+
+def _check_connected_components(f, info, dt):
+    f.is_compatible(info.data_type, dt)
+    f.check_connectivity(info.ndim)
+
+
+def _check_distance_transform(f, info, dt):
+    f.is_compatible(info.data_type, dt)
+    f.check_spacing(info.ndim)
+    f.memory(info.data_type, dt, info.shape)  # the bound on the squared distance
+
+
+def _check_reconstruction(f, info, dt):
+    if dt != info.data_type:
+        raise _abi.UnsupportedDataType(
+            _abi.ERR_UNSUPPORTED_DATA_TYPE,
+            f"reconstruction: the output has the input's data type {info.data_type}, not {dt}")
+    f.is_compatible(info.data_type)
+    f.check_connectivity(info.ndim)
+
+
+def _output_as_given(step, in_data_type, enc):
+    """The default rule: an explicit data type, else the input's; the encoding as given."""
+    return step.get("data_type") or (enc or {}).get("data_type") or in_data_type, enc
+
+
+def _text_key_values(p):
+    """The default fragment: the step's own parameters as key=value."""
+    return " ".join(f"{k}={v}" for k, v in p.items())
+
+
+def _store_pointwise(name: str, src: str, dst: str, p: dict, **kw) -> dict:
+    """A per-element step store -> store: p["args"] holds the filter's own run-config keys."""
+    f = pointwise_filter({"filter": name, **p["args"]})
+    dt, enc = S.pointwise_output(f, S.open_array(src).data_type, kw.pop("data_type", None),
+                                 kw.pop("encoding", None))
+    return S.pointwise(src, dst, [f], [dt], encoding=enc, **kw)
+
+
+@dataclasses.dataclass(frozen=True)
+class StepKind:
+    """Everything zarrs_filter knows about one kind of step. The functions are the module's own
+    and capture nothing (a spawned worker finds the record by its name); the `store` of each
+    looks its function up in `S` when it is called. A kind without `make` is only a store call
+    (for run_rows_parallel) and is outside the accelerated path."""
+    name: str  # in a run config; the subcommand is the same with hyphens
+    help: str = ""  # of the sub-parser
+    arguments: object = None  # (sub-parser): adds its own arguments, after IN and OUT
+    negative_numbers: object = None  # a pattern of arguments that begin with "-" and are values
+    # the step's own keys: names in the argparse namespace, or (namespace) -> (keys, last keys)
+    own: object = ()
+    make: object = None  # (step, info) -> the filter object of a run-config step, validated
+    output: object = _output_as_given  # (step, input type, encoding) -> (data type, encoding)
+    check: object = None  # (filter, info, output type): the checks that need the output type
+    shape: object = None  # (filter, info) -> the output's shape; None: the input's
+    params: object = None  # (filter, step) -> the picklable dict that `store` reads; None: {}
+    text: object = _text_key_values  # (params) -> the step's part of its log line
+    after: object = None  # (params) -> what the log line adds behind the input array
+    store: object = None  # (src, dst, params, **kw) -> stats: the one call into store.*
+    family: str = ""  # "rank", "pointwise", "binary" or "whole_array": the name tuples below
+    rows: bool = True  # chunk rows are independent: --gpus > 1 may split them over processes
+    chain: bool = True  # may be part of a device-resident chain
+    second: object = None  # (key, (step) -> value) of a second input array, "$name" allowed
+    reports: str = None  # the count the filter returns, in the stats and the log
+
+
+# per-element values may be negative (-1e-3 included) and VALUE may be -Infinity; a rank filter's
+# negative KERNEL_HALF_SIZE parses as a value and is rejected as InvalidParameters when the step
+# runs (build_parser says how the patterns take effect)
+_NUMBER = re.compile(r"^-(\d+\.?\d*|\d*\.\d+)([eE][-+]?\d+)?$|^-Infinity$")
+_RANK_NUMBER = re.compile(r"^-\d+(,-?\d+)*$")
+POINTWISE_KEYS = ("offset", "shape", "multiply", "add", "add_first", "min", "max", "value",
+                  "replace")
+
+
+def _rank_kind(name: str, what: str) -> StepKind:
+    return StepKind(
+        name, f"Apply a {what} filter over a box neighbourhood.", _args_rank, _RANK_NUMBER,
+        ("kernel_half_size",), _make_rank,
+        params=lambda f, step: {"kernel_half_size": list(f.kernel_half_size())},
+        store=functools.partial(_store_rank, name), family="rank")
+
+
+def _store_rank(name, src, dst, p, **kw):
+    return S.rank_filter(src, dst, name, p["kernel_half_size"], **kw)
+
+
+def _pointwise_kind(name: str, help: str, arguments, own: tuple, make) -> StepKind:
+    return StepKind(
+        name, help, arguments, _NUMBER, own, make,
+        output=lambda step, in_dt, enc: S.pointwise_output(  # equal: bool, fill value false
+            pointwise_filter(step), in_dt, step.get("data_type"), enc),
+        check=_check_pointwise, shape=lambda f, info: f.output_shape(info.shape),
+        params=lambda f, step: {"args": {k: step[k] for k in POINTWISE_KEYS
+                                         if step.get(k) is not None}},
+        text=lambda p: f"{p['args']}", store=functools.partial(_store_pointwise, name),
+        family="pointwise")
+
+
+# In the order of the subcommands. A summed-area table's chunk rows are not independent: each
+# row's axis-0 sum starts from the previous row's last plane (summed_area_table.rs:69, :94-97).
+# Nor are the whole-array filters': a connected component may span every chunk, and the nearest
+# background element may lie in any; they have no chunks in flight either, so their store
+# functions take no chunk_limit.
+STEP_KINDS = {k.name: k for k in (
+    StepKind(
+        "guided_filter", "Apply a guided filter (edge preserving noise filter).",
+        _args_guided_filter, own=("epsilon", "radius"), make=_make_guided_filter,
+        params=lambda f, step: {"epsilon": float(step["epsilon"]), "radius": int(step["radius"])},
+        store=lambda src, dst, p, **kw: S.guided_filter(src, dst, p["epsilon"], p["radius"],
+                                                        **kw)),
+    StepKind(
+        "downsample", "Downsample an image given a stride.", _args_downsample,
+        own=("stride", "discrete"), make=_make_downsample,
+        shape=lambda f, info: f.output_shape(info.shape),
+        params=lambda f, step: {"stride": list(f.stride),
+                                "discrete": bool(step.get("discrete", False))},
+        store=lambda src, dst, p, **kw: S.downsample(src, dst, p["stride"],
+                                                     discrete=p["discrete"], **kw)),
+    StepKind(
+        "gaussian", "Apply a Gaussian kernel.", _args_gaussian,
+        own=("sigma", "kernel_half_size"), make=_make_gaussian,
+        params=lambda f, step: {"sigma": list(f.sigma),
+                                "kernel_half_size": list(f.kernel_half_size())},
+        store=lambda src, dst, p, **kw: S.gaussian(src, dst, p["sigma"], p["kernel_half_size"],
+                                                   **kw)),
+    StepKind(
+        "summed_area_table", "Compute a summed area table (integral image).",
+        make=lambda step, info: F.SummedAreaTable(),
+        store=lambda src, dst, p, **kw: S.summed_area_table(src, dst, **kw), rows=False),
+    _rank_kind("median", "median"),
+    _rank_kind("minimum", "minimum (grey-scale erosion)"),
+    _rank_kind("maximum", "maximum (grey-scale dilation)"),
+    _pointwise_kind("reencode", "Reencode an array.", None, (), lambda step, info: F.Reencode()),
+    _pointwise_kind(
+        "crop", "Crop an array given an offset and shape.", _args_crop, ("offset", "shape"),
+        lambda step, info: F.Crop(*map(_ints, _need(step, "offset", "shape")))),
+    _pointwise_kind(
+        "rescale", "Rescale array values given a multiplier and offset.", _args_rescale,
+        ("multiply", "add", "add_first"),
+        lambda step, info: F.Rescale(*map(float, _need(step, "multiply", "add")),
+                                     bool(step.get("add_first", False)))),
+    _pointwise_kind(
+        "clamp", "Clamp values between a minimum and maximum.", _args_clamp, ("min", "max"),
+        lambda step, info: F.Clamp(*map(float, _need(step, "min", "max")))),
+    _pointwise_kind(
+        "equal", "Return a binary image where the input is equal to some value.", _args_equal,
+        ("value",), lambda step, info: F.Equal(*_need(step, "value"))),
+    _pointwise_kind(
+        "replace_value", "Replace a value with another value.", _args_replace_value,
+        ("value", "replace"), lambda step, info: F.ReplaceValue(*_need(step, "value", "replace"))),
+    StepKind(
+        "arithmetic", "Combine two arrays of one shape element by element.", _args_arithmetic,
+        own=lambda a: ({"operator": a.operator.replace("-", "_"), "other": a.other}, {}),
+        make=lambda step, info: F.Arithmetic(arithmetic_args(step)[0]),
+        params=lambda f, step: {"operator": f.operator, "other": str(step["other"])},
+        text=lambda p: p["operator"], after=lambda p: f" with {p['other']}",
+        store=lambda src, dst, p, **kw: S.arithmetic(src, p["other"], dst, p["operator"], **kw),
+        family="binary", chain=False, second=("other", lambda step: arithmetic_args(step)[1])),
+    StepKind(
+        "connected_components", "Label the connected sets of non-zero elements.",
+        _args_connectivity, own=("connectivity",),
+        make=lambda step, info: F.ConnectedComponents(connectivity_of(step)),
+        output=lambda step, in_dt, enc: S.connected_components_output(  # uint32, fill value 0
+            step.get("data_type"), enc),
+        check=_check_connected_components,
+        params=lambda f, step: {"connectivity": f.connectivity},
+        store=lambda src, dst, p, chunk_limit=0, **kw: S.connected_components(
+            src, dst, p["connectivity"], **kw),
+        family="whole_array", rows=False, reports="components"),
+    StepKind(
+        "distance_transform", "Exact Euclidean distance to the nearest zero element.",
+        _args_distance_transform, own=("spacing", "squared"), make=distance_transform_of,
+        output=lambda step, in_dt, enc: S.distance_transform_output(  # float32, uint32 squared
+            bool(step.get("squared", False)), step.get("data_type"), enc),
+        check=_check_distance_transform,
+        params=lambda f, step: {"spacing": None if f.spacing is None else list(f.spacing),
+                                "squared": f.squared},
+        text=lambda p: f"spacing={p['spacing'] or 'ones'} squared={p['squared']}",
+        store=lambda src, dst, p, chunk_limit=0, **kw: S.distance_transform(
+            src, dst, p["spacing"], p["squared"], **kw),
+        family="whole_array", rows=False),
+    StepKind(
+        "label_size_filter", "Keep the labels of a label array whose element count is in range.",
+        _args_label_size_filter,
+        own=lambda a: ({"min_size": a.min_size, "max_size": a.max_size,
+                        "relabel": not a.no_relabel}, {}),
+        make=label_size_filter_of,
+        output=lambda step, in_dt, enc: S.label_size_filter_output(  # the input's, fill value 0
+            in_dt, step.get("data_type"), enc),
+        check=lambda f, info, dt: f.is_compatible(info.data_type, dt),
+        params=lambda f, step: {"min_size": f.min_size, "max_size": f.max_size,
+                                "relabel": f.relabel},
+        store=lambda src, dst, p, chunk_limit=0, **kw: S.label_size_filter(
+            src, dst, p["min_size"], p["max_size"], p["relabel"], **kw),
+        family="whole_array", rows=False, reports="components"),
+    StepKind(
+        "reconstruction", "Morphological reconstruction of a marker under the mask IN.",
+        _args_reconstruction, own=_own_reconstruction,
+        make=lambda step, info: reconstruction_of(step)[0], check=_check_reconstruction,
+        params=lambda f, step: {
+            "marker": None if step.get("marker") is None else str(step["marker"]),
+            "mode": f.mode, "method": f.method, "connectivity": f.connectivity,
+            "h": f.h if f.mode in ("h_maxima", "h_minima") else None},
+        text=lambda p: (f"mode={p['mode']} method={p['method']} connectivity={p['connectivity']}"
+                        + (f" h={p['h']}" if p["h"] is not None else "")),
+        after=lambda p: f" marker {p['marker']}" if p["marker"] is not None else "",
+        store=lambda src, dst, p, chunk_limit=0, **kw: S.reconstruction(
+            src, dst, p["marker"], p["method"] if p["marker"] else "dilation", p["connectivity"],
+            p["mode"], p["h"], **kw),
+        family="whole_array", rows=False,
+        second=("marker", lambda step: reconstruction_of(step)[1]), reports="rounds"),
+    StepKind(  # a zarrs_ome level with --gaussian-sigma
+        "downsample_gaussian",
+        store=lambda src, dst, p, **kw: S.downsample_gaussian(
+            src, dst, p["stride"], p["sigma"], p["kernel_half_size"], **kw)),
+)}
+
+
+def _family(family: str) -> tuple:
+    return tuple(k.name for k in STEP_KINDS.values() if k.family == family)
+
+
+POINTWISE, RANK = _family("pointwise"), _family("rank")
+BINARY = _family("binary")  # two arrays in: "input" and "other"
+WHOLE_ARRAY = _family("whole_array")  # no chunk rows at all: the array is the unit of work
+ON_PATH = tuple(k.name for k in STEP_KINDS.values() if k.make is not None)
+
+
+def rows_splittable(name: str) -> bool:
+    """Whether a store step's output chunk rows are independent, so that --gpus > 1 may split
+    them over processes (StepKind.rows)."""
+    return name not in STEP_KINDS or STEP_KINDS[name].rows
+
+
+def step_encoding(step: dict, in_data_type: str):
+    """The reencoding a step's output array is created with: encoding_of(step), and for a filter
+    that sets its own output type (equal: bool, fill value false) that type when the step gives
+    none (output_array_builder, filter_traits.rs:47-82)."""
+    kind, enc = STEP_KINDS.get(step.get("filter")), encoding_of(step)
+    return enc if kind is None else kind.output(step, in_data_type, enc)[1]
+
+
+def _step_params(step, info):
+    """(filter object, output shape, output data type) of a run-config step on an input array."""
+    kind = STEP_KINDS[step.get("filter")]
+    f = kind.make(step, info)
+    dt, _enc = kind.output(step, info.data_type, encoding_of(step))
+    if kind.check is not None:
+        kind.check(f, info, dt)
+    return f, (tuple(info.shape) if kind.shape is None else kind.shape(f, info)), dt
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="zarrs_filter",
                                  description="Apply filters to a Zarr V3 array on an MI355X.")
@@ -247,207 +703,42 @@ def build_parser() -> argparse.ArgumentParser:
                     help="in a device-resident chain, launch consecutive per-element steps one "
                          "by one")
     sub = ap.add_subparsers(dest="filter")
-    g = sub.add_parser("guided-filter", help="Apply a guided filter (edge preserving noise filter).")
-    g.add_argument("input")
-    g.add_argument("output")
-    g.add_argument("epsilon", type=float)
-    g.add_argument("radius", type=int)
-    _add_reencode_args(g)
-    d = sub.add_parser("downsample", help="Downsample an image given a stride.")
-    d.add_argument("input")
-    d.add_argument("output")
-    d.add_argument("stride", type=_parse_stride)
-    d.add_argument("--discrete", action="store_true")
-    _add_reencode_args(d)
-    gs = sub.add_parser("gaussian", help="Apply a Gaussian kernel.")
-    gs.add_argument("input")
-    gs.add_argument("output")
-    gs.add_argument("sigma", type=_parse_floats)
-    gs.add_argument("kernel_half_size", type=_parse_stride)
-    _add_reencode_args(gs)
-    sa = sub.add_parser("summed-area-table", help="Compute a summed area table (integral image).")
-    sa.add_argument("input")
-    sa.add_argument("output")
-    _add_reencode_args(sa)
-    # the per-element filters; their numbers may be negative (-1e-3 included) and VALUE may be
-    # -Infinity, which argparse would otherwise take for options. This sets argparse's
-    # `_negative_number_matcher`, an undocumented attribute of ArgumentParser (CPython 3.2 to
-    # 3.13 consult it in `_parse_optional`): an argument that matches it is a positional as long
-    # as the parser has no option that looks like a negative number. tests/test_pointwise.py
-    # (test_subcommand_grammar_of_the_six) fails if a Python version stops honouring it.
-    number = re.compile(r"^-(\d+\.?\d*|\d*\.\d+)([eE][-+]?\d+)?$|^-Infinity$")
-
-    def pointwise(name, help):
-        p = sub.add_parser(name, help=help)
-        p._negative_number_matcher = number
+    for kind in STEP_KINDS.values():
+        if kind.make is None:
+            continue
+        p = sub.add_parser(kind.name.replace("_", "-"), help=kind.help)
+        if kind.negative_numbers is not None:
+            # argparse would take such arguments for options. This sets argparse's
+            # `_negative_number_matcher`, an undocumented attribute of ArgumentParser (CPython
+            # 3.2 to 3.13 consult it in `_parse_optional`): an argument that matches it is a
+            # positional as long as the parser has no option that looks like a negative number.
+            # tests/test_pointwise.py (test_subcommand_grammar_of_the_six) fails if a Python
+            # version stops honouring it.
+            p._negative_number_matcher = kind.negative_numbers
         p.add_argument("input")
         p.add_argument("output")
-        return p
-
-    # the rank filters (an extension); a negative KERNEL_HALF_SIZE parses as a value and is
-    # rejected as InvalidParameters when the step runs
-    rank_number = re.compile(r"^-\d+(,-?\d+)*$")
-    for name, what in (("median", "median"), ("minimum", "minimum (grey-scale erosion)"),
-                       ("maximum", "maximum (grey-scale dilation)")):
-        rk = sub.add_parser(name, help=f"Apply a {what} filter over a box neighbourhood.")
-        rk._negative_number_matcher = rank_number
-        rk.add_argument("input")
-        rk.add_argument("output")
-        rk.add_argument("kernel_half_size", type=_parse_stride)
-        _add_reencode_args(rk)
-
-    re_ = pointwise("reencode", "Reencode an array.")
-    _add_reencode_args(re_)
-    cr = pointwise("crop", "Crop an array given an offset and shape.")
-    cr.add_argument("offset", type=_parse_stride)
-    cr.add_argument("shape", type=_parse_stride)
-    _add_reencode_args(cr)
-    rs = pointwise("rescale", "Rescale array values given a multiplier and offset.")
-    rs.add_argument("multiply", type=float)
-    rs.add_argument("add", type=float)
-    rs.add_argument("--add-first", action="store_true",
-                    help="perform the addition before the multiplication")
-    _add_reencode_args(rs)
-    cl = pointwise("clamp", "Clamp values between a minimum and maximum.")
-    cl.add_argument("min", type=float)
-    cl.add_argument("max", type=float)
-    _add_reencode_args(cl)
-    eq = pointwise("equal", "Return a binary image where the input is equal to some value.")
-    eq.add_argument("value", type=_parse_fill_value)
-    _add_reencode_args(eq)
-    rv = pointwise("replace-value", "Replace a value with another value.")
-    rv.add_argument("value", type=_parse_fill_value)
-    rv.add_argument("replace", type=_parse_fill_value)
-    _add_reencode_args(rv)
-    ar = sub.add_parser("arithmetic", help="Combine two arrays of one shape element by element.")
-    ar.add_argument("input")
-    ar.add_argument("output")
-    ar.add_argument("operator", choices=[o.replace("_", "-") for o in _abi.AR_OPERATORS])
-    ar.add_argument("other")
-    _add_reencode_args(ar)
-    cc = sub.add_parser("connected-components",
-                        help="Label the connected sets of non-zero elements.")
-    cc.add_argument("input")
-    cc.add_argument("output")
-    cc.add_argument("--connectivity", type=int, default=1,
-                    help="neighbours differ on at most this many axes (1: faces, the default; "
-                         "the rank: the full neighbourhood)")
-    _add_reencode_args(cc)
-    dtr = sub.add_parser("distance-transform",
-                         help="Exact Euclidean distance to the nearest zero element.")
-    dtr.add_argument("input")
-    dtr.add_argument("output")
-    dtr.add_argument("--spacing", type=_parse_stride, default=None,
-                     help="the length of a step along each axis: comma delimited integers >= 1, "
-                          "one per axis (default: all 1)")
-    dtr.add_argument("--squared", action="store_true",
-                     help="store the squared distance (an exact integer; uint32 by default)")
-    _add_reencode_args(dtr)
-    lsf = sub.add_parser("label-size-filter",
-                         help="Keep the labels of a label array whose element count is in range.")
-    lsf.add_argument("input")
-    lsf.add_argument("output")
-    lsf.add_argument("--min-size", type=int, default=1,
-                     help="the fewest elements of a label that is kept (default 1)")
-    lsf.add_argument("--max-size", type=int, default=None,
-                     help="the most elements of a label that is kept (default: no bound)")
-    lsf.add_argument("--no-relabel", action="store_true",
-                     help="kept labels keep their values (default: renumbered 1 .. K' in "
-                          "increasing order)")
-    _add_reencode_args(lsf)
-    rc = sub.add_parser("reconstruction",
-                        help="Morphological reconstruction of a marker under the mask IN.")
-    rc.add_argument("input")
-    rc.add_argument("output")
-    how = rc.add_mutually_exclusive_group(required=True)
-    how.add_argument("--marker", default=None,
-                     help="the marker: a second array of IN's shape and data type")
-    how.add_argument("--fill-holes", action="store_true",
-                     help="by erosion from the array's border: fills the holes of a mask of "
-                          "background")
-    how.add_argument("--h-maxima", type=float, default=None, metavar="H",
-                     help="by dilation of IN - H: suppresses maxima lower than H")
-    how.add_argument("--h-minima", type=float, default=None, metavar="H",
-                     help="by erosion of IN + H: suppresses minima shallower than H")
-    rc.add_argument("--method", choices=["dilation", "erosion"], default=None,
-                    help="with --marker only (default dilation)")
-    rc.add_argument("--connectivity", type=int, default=1,
-                    help="neighbours differ on at most this many axes (1: faces, the default; "
-                         "the rank: the full neighbourhood)")
-    _add_reencode_args(rc)
+        if kind.arguments is not None:
+            kind.arguments(p)
+        _add_reencode_args(p)
     return ap
 
 
 def _steps_from_cli(a) -> list:
-    if a.filter == "guided-filter":
-        return [{"filter": "guided_filter", "input": a.input, "output": a.output,
-                 "epsilon": a.epsilon, "radius": a.radius, "data_type": a.data_type,
-                 "chunk_limit": a.filter_chunk_limit, **_reencode_of(a)}]
-    if a.filter == "downsample":
-        return [{"filter": "downsample", "input": a.input, "output": a.output,
-                 "stride": a.stride, "discrete": a.discrete, "data_type": a.data_type,
-                 "chunk_limit": a.filter_chunk_limit, **_reencode_of(a)}]
-    if a.filter == "gaussian":
-        return [{"filter": "gaussian", "input": a.input, "output": a.output, "sigma": a.sigma,
-                 "kernel_half_size": a.kernel_half_size, "data_type": a.data_type,
-                 "chunk_limit": a.filter_chunk_limit, **_reencode_of(a)}]
-    if a.filter == "summed-area-table":
-        return [{"filter": "summed_area_table", "input": a.input, "output": a.output,
-                 "data_type": a.data_type, "chunk_limit": a.filter_chunk_limit,
-                 **_reencode_of(a)}]
-    if a.filter in RANK:
-        return [{"filter": a.filter, "input": a.input, "output": a.output,
-                 "kernel_half_size": a.kernel_half_size, "data_type": a.data_type,
-                 "chunk_limit": a.filter_chunk_limit, **_reencode_of(a)}]
-    own = {"reencode": (), "crop": ("offset", "shape"),
-           "rescale": ("multiply", "add", "add_first"), "clamp": ("min", "max"),
-           "equal": ("value",), "replace-value": ("value", "replace")}
-    if a.filter in own:
-        return [{"filter": a.filter.replace("-", "_"), "input": a.input, "output": a.output,
-                 **{k: getattr(a, k) for k in own[a.filter]}, "data_type": a.data_type,
-                 "chunk_limit": a.filter_chunk_limit, **_reencode_of(a)}]
-    if a.filter == "arithmetic":
-        return [{"filter": "arithmetic", "input": a.input, "output": a.output,
-                 "operator": a.operator.replace("-", "_"), "other": a.other,
-                 "data_type": a.data_type, "chunk_limit": a.filter_chunk_limit,
-                 **_reencode_of(a)}]
-    if a.filter == "connected-components":
-        return [{"filter": "connected_components", "input": a.input, "output": a.output,
-                 "connectivity": a.connectivity, "data_type": a.data_type,
-                 "chunk_limit": a.filter_chunk_limit, **_reencode_of(a)}]
-    if a.filter == "distance-transform":
-        return [{"filter": "distance_transform", "input": a.input, "output": a.output,
-                 "spacing": a.spacing, "squared": a.squared, "data_type": a.data_type,
-                 "chunk_limit": a.filter_chunk_limit, **_reencode_of(a)}]
-    if a.filter == "label-size-filter":
-        return [{"filter": "label_size_filter", "input": a.input, "output": a.output,
-                 "min_size": a.min_size, "max_size": a.max_size, "relabel": not a.no_relabel,
-                 "data_type": a.data_type, "chunk_limit": a.filter_chunk_limit,
-                 **_reencode_of(a)}]
-    if a.filter == "reconstruction":
-        if a.method is not None and a.marker is None:
-            raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS,
-                                         "reconstruction: --method is only valid with --marker")
-        mode, h = "marker", None
-        if a.fill_holes:
-            mode = "fill_holes"
-        elif a.h_maxima is not None:
-            mode, h = "h_maxima", a.h_maxima
-        elif a.h_minima is not None:
-            mode, h = "h_minima", a.h_minima
-        step = {"filter": "reconstruction", "input": a.input, "output": a.output, "mode": mode,
-                "connectivity": a.connectivity, "data_type": a.data_type,
-                "chunk_limit": a.filter_chunk_limit, **_reencode_of(a)}
-        if a.marker is not None:
-            step.update(marker=a.marker, method=a.method or "dilation")
-        if h is not None:
-            step["h"] = h
-        return [step]
-    return []
+    if a.filter is None:
+        return []
+    kind = STEP_KINDS[a.filter.replace("-", "_")]
+    own, last = kind.own(a) if callable(kind.own) else ({k: getattr(a, k) for k in kind.own}, {})
+    return [{"filter": kind.name, "input": a.input, "output": a.output, **own,
+             "data_type": a.data_type, "chunk_limit": a.filter_chunk_limit, **_reencode_of(a),
+             **last}]
+
+
+def _is_named_temp(p) -> bool:
+    return isinstance(p, str) and p.startswith("$")
 
 
 def _is_temp(p) -> bool:
-    return p is None or (isinstance(p, str) and p.startswith("$"))
+    return p is None or _is_named_temp(p)
 
 
 def plan_chains(steps: list) -> list:
@@ -460,13 +751,15 @@ def plan_chains(steps: list) -> list:
     for st in steps:
         for key in ("input", "output", "other", "marker"):
             v = st.get(key)
-            if isinstance(v, str) and v.startswith("$"):
+            if _is_named_temp(v):
                 refs[v] = refs.get(v, 0) + 1
 
+    def may_chain(st):
+        kind = STEP_KINDS.get(st.get("filter"))
+        return (kind is None or kind.chain) and st.get("marker") is None
+
     def linked(k):
-        if steps[k].get("filter") in BINARY or steps[k + 1].get("filter") in BINARY:
-            return False
-        if steps[k].get("marker") is not None or steps[k + 1].get("marker") is not None:
+        if not (may_chain(steps[k]) and may_chain(steps[k + 1])):
             return False
         out, nxt = steps[k].get("output"), steps[k + 1].get("input")
         if not _is_temp(out):
@@ -484,222 +777,6 @@ def plan_chains(steps: list) -> list:
             chains.append((i, j))
         i = j + 1
     return chains
-
-
-def pointwise_filter(step: dict):
-    """The per-element filter object of a run-config step (keys as the reference's *Arguments
-    structs: offset, shape; multiply, add, add_first; min, max; value; value, replace)."""
-    from . import filter as F
-    name = step.get("filter")
-
-    def need(*keys):
-        missing = [k for k in keys if step.get(k) is None]
-        if missing:
-            raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS,
-                                         f"{name} needs {', '.join(missing)}")
-        return [step[k] for k in keys]
-
-    def ints(v):
-        return _parse_stride(v) if isinstance(v, str) else [int(x) for x in v]
-
-    if name == "reencode":
-        return F.Reencode()
-    if name == "crop":
-        offset, shape = need("offset", "shape")
-        return F.Crop(ints(offset), ints(shape))
-    if name == "rescale":
-        multiply, add = need("multiply", "add")
-        return F.Rescale(float(multiply), float(add), bool(step.get("add_first", False)))
-    if name == "clamp":
-        lo, hi = need("min", "max")
-        return F.Clamp(float(lo), float(hi))
-    if name == "equal":
-        return F.Equal(need("value")[0])
-    if name == "replace_value":
-        value, replace = need("value", "replace")
-        return F.ReplaceValue(value, replace)
-    raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS, f"{name} is not a per-element filter")
-
-
-def arithmetic_args(step: dict):
-    """(operator, other) of an arithmetic run-config step."""
-    from .filter import arithmetic_operator
-    missing = [k for k in ("operator", "other") if step.get(k) is None]
-    if missing:
-        raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS,
-                                     f"arithmetic needs {', '.join(missing)}")
-    arithmetic_operator(step["operator"])  # InvalidParameters for an unknown name
-    return str(step["operator"]).replace("-", "_"), step["other"]
-
-
-def step_encoding(step: dict, in_data_type: str):
-    """The reencoding a step's output array is created with: encoding_of(step), and for a
-    per-element filter that sets its own output type (equal: bool, fill value false) that type
-    when the step gives none (output_array_builder, filter_traits.rs:47-82)."""
-    enc = encoding_of(step)
-    if step.get("filter") in POINTWISE:
-        _dt, enc = S.pointwise_output(pointwise_filter(step), in_data_type,
-                                      step.get("data_type"), enc)
-    if step.get("filter") == "connected_components":  # labels: uint32, fill value 0
-        _dt, enc = S.connected_components_output(step.get("data_type"), enc)
-    if step.get("filter") == "distance_transform":  # float32, or uint32 squared; fill value 0
-        _dt, enc = S.distance_transform_output(bool(step.get("squared", False)),
-                                               step.get("data_type"), enc)
-    if step.get("filter") == "label_size_filter":  # the input's type; fill value 0
-        _dt, enc = S.label_size_filter_output(in_data_type, step.get("data_type"), enc)
-    return enc
-
-
-def label_size_filter_of(step: dict):
-    """The size filter of a run-config step: "min_size" (default 1) and "max_size" (default
-    none) integers, "relabel" a boolean (default true)."""
-    from . import filter as F
-    try:
-        mn = 1 if step.get("min_size") is None else int(step["min_size"])
-        mx = None if step.get("max_size") is None else int(step["max_size"])
-    except (TypeError, ValueError):
-        raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS,
-                                     "label_size_filter: min_size and max_size are "
-                                     "integers") from None
-    relabel = step.get("relabel")
-    return S.SizeFilterStep(F.LabelSizeFilter(mn, mx, True if relabel is None else bool(relabel)))
-
-
-def connectivity_of(step: dict) -> int:
-    """The connectivity of a connected_components run-config step (default 1: faces)."""
-    c = step.get("connectivity")
-    try:
-        return 1 if c is None else int(c)
-    except (TypeError, ValueError):
-        raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS,
-                                     f"connected_components: connectivity {c!r} is not an "
-                                     "integer") from None
-
-
-def reconstruction_of(step: dict):
-    """(Reconstruction, marker) of a run-config step: "marker" a path or the "$name" of an earlier
-    step's output (then "mode" is marker, or omitted), or "mode" one of fill_holes, h_maxima,
-    h_minima with "h" for the last two; "method" dilation (default) or erosion, with a marker
-    only; "connectivity" an integer (default 1)."""
-    from . import filter as F
-    marker = step.get("marker")
-    mode = step.get("mode") or ("marker" if marker is not None else None)
-    if mode is None:
-        raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS,
-                                     "reconstruction needs a marker or a mode (fill_holes, "
-                                     "h_maxima, h_minima)")
-    mode = str(mode).replace("-", "_")
-    if (mode == "marker") != (marker is not None):
-        raise _abi.InvalidParameters(
-            _abi.ERR_INVALID_PARAMETERS,
-            "reconstruction: mode marker needs a marker" if marker is None else
-            f"reconstruction: {mode} makes its marker from the mask; no marker is given")
-    if step.get("method") is not None and marker is None:
-        raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS,
-                                     "reconstruction: a method is only valid with a marker")
-    c = step.get("connectivity")
-    try:
-        c = 1 if c is None else int(c)
-    except (TypeError, ValueError):
-        raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS,
-                                     f"reconstruction: connectivity {c!r} is not an "
-                                     "integer") from None
-    return F.Reconstruction(step.get("method") or "dilation", c, mode, step.get("h")), marker
-
-
-def distance_transform_of(step: dict):
-    """The DistanceTransform of a run-config step: "spacing" a list (or a comma delimited string)
-    of integers >= 1, default all 1; "squared" a boolean, default false."""
-    from . import filter as F
-    sp = step.get("spacing")
-    if isinstance(sp, str):
-        sp = [x.strip() for x in sp.split(",") if x.strip()]
-        try:
-            sp = [int(x) for x in sp]
-        except ValueError:
-            raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS,
-                                         f"distance_transform: spacing {step['spacing']!r} is "
-                                         "not a list of integers") from None
-    elif sp is not None and not isinstance(sp, (list, tuple)):
-        sp = [sp]
-    return F.DistanceTransform(sp, bool(step.get("squared", False)))
-
-
-def _step_params(step, info):
-    """(filter object, output shape, output data type) of a run-config step on an input array."""
-    from . import filter as F
-    name = step.get("filter")
-    if name in POINTWISE:
-        f = pointwise_filter(step)
-        dt, _enc = S.pointwise_output(f, info.data_type, step.get("data_type"),
-                                      encoding_of(step))
-        f.is_compatible(info.data_type, dt)
-        f.op(info.data_type, dt)  # value / replace must fit the types
-        return f, f.output_shape(info.shape), dt
-    if name == "connected_components":
-        f = F.ConnectedComponents(connectivity_of(step))
-        dt, _enc = S.connected_components_output(step.get("data_type"), encoding_of(step))
-        f.is_compatible(info.data_type, dt)
-        f.check_connectivity(info.ndim)
-        return f, tuple(info.shape), dt
-    if name == "distance_transform":
-        f = distance_transform_of(step)
-        dt, _enc = S.distance_transform_output(f.squared, step.get("data_type"),
-                                               encoding_of(step))
-        f.is_compatible(info.data_type, dt)
-        f.check_spacing(info.ndim)
-        f.memory(info.data_type, dt, info.shape)  # the bound on the squared distance
-        return f, tuple(info.shape), dt
-    if name == "label_size_filter":
-        f = label_size_filter_of(step)
-        dt, _enc = S.label_size_filter_output(info.data_type, step.get("data_type"),
-                                              encoding_of(step))
-        f.is_compatible(info.data_type, dt)
-        return f, tuple(info.shape), dt
-    dt = step.get("data_type") or (encoding_of(step) or {}).get("data_type") or info.data_type
-    if name == "reconstruction":
-        f, _marker = reconstruction_of(step)
-        if dt != info.data_type:
-            raise _abi.UnsupportedDataType(
-                _abi.ERR_UNSUPPORTED_DATA_TYPE,
-                f"reconstruction: the output has the input's data type {info.data_type}, not {dt}")
-        f.is_compatible(info.data_type)
-        f.check_connectivity(info.ndim)
-        return f, tuple(info.shape), dt
-    if name == "guided_filter":
-        if "epsilon" not in step or "radius" not in step:
-            raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS,
-                                         "guided_filter needs epsilon and radius")
-        return F.GuidedFilter(float(step["epsilon"]), int(step["radius"])), tuple(info.shape), dt
-    if name == "gaussian":
-        sigma, half = step.get("sigma"), step.get("kernel_half_size")
-        sigma = _parse_floats(sigma) if isinstance(sigma, str) else sigma
-        half = _parse_stride(half) if isinstance(half, str) else half
-        if not sigma or not half or len(sigma) != info.ndim or len(half) != info.ndim:
-            raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS,
-                                         "gaussian sigma and kernel_half_size need one entry "
-                                         "per axis")
-        return F.Gaussian(sigma, half), tuple(info.shape), dt
-    if name == "summed_area_table":
-        return F.SummedAreaTable(), tuple(info.shape), dt
-    if name == "arithmetic":
-        return F.Arithmetic(arithmetic_args(step)[0]), tuple(info.shape), dt
-    if name in RANK:
-        half = step.get("kernel_half_size")
-        half = _parse_stride(half) if isinstance(half, str) else half
-        if half is None:
-            raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS,
-                                         f"{name} needs kernel_half_size")
-        half = [int(h) for h in half]
-        F.check_rank_half(name, half, info.ndim)
-        return F.RankFilter(name, half), tuple(info.shape), dt
-    stride = step.get("stride")
-    stride = _parse_stride(stride) if isinstance(stride, str) else stride
-    if not stride or len(stride) != info.ndim:
-        raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS,
-                                     "downsample stride must match the array rank")
-    f = F.Downsample(stride, discrete=bool(step.get("discrete", False)))
-    return f, f.output_shape(info.shape), dt
 
 
 def _nbytes(shape, data_type) -> int:
@@ -749,7 +826,6 @@ def run_device_chain(steps: list, paths: list, device: int = 0, nthreads: int = 
     None (nothing done) when the chain's arrays do not fit `budget_frac` of the free device
     memory, in which case the caller runs it store -> store."""
     import torch
-    from . import filter as F
     # shapes / types of every array of the chain (metadata only)
     plan, info = [], S.open_array(paths[0])
     for k, step in enumerate(steps):
@@ -814,12 +890,9 @@ def run_device_chain(steps: list, paths: list, device: int = 0, nthreads: int = 
         t_k = time.perf_counter() - t1
         log(f"{i if j == i else f'{i}-{j}'}: {names} device-resident {list(x.shape)} {x_dt} -> "
             f"{list(y.shape)} {out_info.data_type} in {t_k:.3f}s")
-        components = None
-        if names in ("connected_components", "label_size_filter"):  # the steps with a count
-            components = int(ret)
-            log(f"   {components} components")
-        if names == "reconstruction":
-            log(f"   {int(ret)} rounds")
+        reports = STEP_KINDS[names].reports if j == i else None  # the steps with a count
+        if reports:
+            log(f"   {int(ret)} {reports}")
         if names in WHOLE_ARRAY:
             ctx.release_scratch()  # whole-array scratch: not held through the rest of the chain
         for k in range(i, j + 1):
@@ -832,10 +905,8 @@ def run_device_chain(steps: list, paths: list, device: int = 0, nthreads: int = 
             if j > i:
                 st["fused_into" if not carrier else "fused_steps"] = (
                     j if not carrier else list(range(i, j + 1)))
-            if components is not None:
-                st["components"] = components
-            if names == "reconstruction":
-                st["rounds"] = int(ret)
+            if reports:
+                st[reports] = int(ret)
             results.append(st)
         x, x_dt, x_chunk = y, out_info.data_type, out_info.chunk_shape
     t2 = time.perf_counter()
@@ -852,36 +923,16 @@ def _rows_worker(name: str, src: str, dst: str, params: dict, device: int, rows,
     budget of this process (ZT_STORE_HOST_MEMORY / ZT_STORE_DEVICE_MEMORY, its share)."""
     os.environ.update(env or {})
     S.set_store_empty_chunks(params.get("store_empty_chunks", True))
-    cols = None
-    if isinstance(rows, tuple) and len(rows) == 2 and isinstance(rows[0], tuple):
-        rows, cols = rows  # ((row range), (column range)): a (t, z) block
-    kw = dict(device=device, rows=rows, nthreads=nthreads, erase=False, finish=False,
-              encoding=params.get("encoding"), data_type=params.get("data_type"),
-              chunk_limit=params.get("chunk_limit") or 0)
-    if name == "guided_filter":
-        return S.guided_filter(src, dst, params["epsilon"], params["radius"], cols=cols, **kw)
-    if name == "gaussian":
-        return S.gaussian(src, dst, params["sigma"], params["kernel_half_size"], **kw)
-    if name in RANK:
-        return S.rank_filter(src, dst, name, params["kernel_half_size"], **kw)
-    if name in POINTWISE:
-        return _store_pointwise(name, src, dst, params["args"], **kw)
-    if name == "arithmetic":
-        return S.arithmetic(src, params["other"], dst, params["operator"], **kw)
-    if name == "downsample_gaussian":  # a zarrs_ome level with --gaussian-sigma
-        return S.downsample_gaussian(src, dst, params["stride"], params["sigma"],
-                                     params["kernel_half_size"], **kw)
-    if name != "downsample":
+    kind = STEP_KINDS.get(name)
+    if kind is None or not kind.rows:
         raise _abi.FilterError(_abi.ERR_OTHER, f"no store step for filter {name!r}")
-    return S.downsample(src, dst, params["stride"], discrete=params["discrete"], **kw)
-
-
-def _store_pointwise(name: str, src: str, dst: str, args: dict, **kw) -> dict:
-    """A per-element step store -> store: `args` holds the filter's own run-config keys."""
-    f = pointwise_filter({"filter": name, **args})
-    dt, enc = S.pointwise_output(f, S.open_array(src).data_type, kw.pop("data_type", None),
-                                 kw.pop("encoding", None))
-    return S.pointwise(src, dst, [f], [dt], encoding=enc, **kw)
+    kw = {}
+    if isinstance(rows, tuple) and len(rows) == 2 and isinstance(rows[0], tuple):
+        rows, kw["cols"] = rows  # ((row range), (column range)): a (t, z) block
+    return kind.store(src, dst, params, device=device, rows=rows, nthreads=nthreads, erase=False,
+                      finish=False, encoding=params.get("encoding"),
+                      data_type=params.get("data_type"),
+                      chunk_limit=params.get("chunk_limit") or 0, **kw)
 
 
 def run_rows_parallel(name: str, src: str, dst: str, params: dict, out_shape, gpus: int,
@@ -989,7 +1040,7 @@ def run(steps: list, exists: str = "erase", tmp: str | None = None,
                 return d
             raise _abi.InvalidParameters(_abi.ERR_INVALID_PARAMETERS,
                                          "the first filter needs an input")
-        if isinstance(p, str) and p.startswith("$"):
+        if _is_named_temp(p):
             if p not in temps:
                 temps[p] = tempfile.mkdtemp(prefix=p[1:] + "_", dir=tmp_root)
                 made.append(temps[p])
@@ -1006,135 +1057,42 @@ def run(steps: list, exists: str = "erase", tmp: str | None = None,
 
     def store_step(i, step, src, dst):
         name = step.get("filter")
+        kind = STEP_KINDS[name]
         limit = step.get("chunk_limit") or chunk_limit or 0  # chunks in flight, not threads
         info = S.open_array(src)
+        if kind.second is not None and _is_named_temp(step.get(kind.second[0])):
+            # written by an earlier step (checked before the run)
+            step = {**step, kind.second[0]: temps[step[kind.second[0]]]}
         f, out_shape, _dt = _step_params(step, info)
-        enc = encoding_of(step)
-        if name == "guided_filter":
-            params = {"epsilon": float(step["epsilon"]), "radius": int(step["radius"])}
-            log(f"{i}: guided_filter epsilon={params['epsilon']} radius={params['radius']} "
-                f"{src} ({info.data_type} {list(info.shape)}) -> {dst}")
-        elif name == "gaussian":
-            params = {"sigma": list(f.sigma), "kernel_half_size": list(f.kernel_half_size())}
-            log(f"{i}: gaussian sigma={params['sigma']} "
-                f"kernel_half_size={params['kernel_half_size']} "
-                f"{src} ({info.data_type} {list(info.shape)}) -> {dst}")
-        elif name == "summed_area_table":
-            params = {}
-            log(f"{i}: summed_area_table {src} ({info.data_type} {list(info.shape)}) -> {dst}")
-        elif name in RANK:
-            params = {"kernel_half_size": list(f.kernel_half_size())}
-            log(f"{i}: {name} kernel_half_size={params['kernel_half_size']} "
-                f"{src} ({info.data_type} {list(info.shape)}) -> {dst}")
-        elif name in POINTWISE:
-            own = ("offset", "shape", "multiply", "add", "add_first", "min", "max", "value",
-                   "replace")
-            params = {"args": {k: step[k] for k in own if step.get(k) is not None}}
-            log(f"{i}: {name} {params['args']} {src} ({info.data_type} {list(info.shape)}) "
-                f"-> {dst}")
-            enc = step_encoding(step, info.data_type)  # equal: bool, fill value false
-        elif name == "arithmetic":
-            other = step["other"]
-            if isinstance(other, str) and other.startswith("$"):
-                other = temps[other]  # written by an earlier step (checked before the run)
-            params = {"operator": f.operator, "other": str(other)}
-            log(f"{i}: arithmetic {f.operator} {src} ({info.data_type} {list(info.shape)}) "
-                f"with {other} -> {dst}")
-        elif name == "connected_components":
-            params = {"connectivity": f.connectivity}
-            log(f"{i}: connected_components connectivity={f.connectivity} "
-                f"{src} ({info.data_type} {list(info.shape)}) -> {dst}")
-        elif name == "distance_transform":
-            params = {"spacing": None if f.spacing is None else list(f.spacing),
-                      "squared": f.squared}
-            log(f"{i}: distance_transform spacing={params['spacing'] or 'ones'} "
-                f"squared={f.squared} {src} ({info.data_type} {list(info.shape)}) -> {dst}")
-        elif name == "label_size_filter":
-            params = {"min_size": f.min_size, "max_size": f.max_size, "relabel": f.relabel}
-            log(f"{i}: label_size_filter min_size={f.min_size} max_size={f.max_size} "
-                f"relabel={f.relabel} {src} ({info.data_type} {list(info.shape)}) -> {dst}")
-        elif name == "reconstruction":
-            marker = reconstruction_of(step)[1]
-            if isinstance(marker, str) and marker.startswith("$"):
-                marker = temps[marker]  # written by an earlier step (checked before the run)
-            params = {"marker": None if marker is None else str(marker), "mode": f.mode,
-                      "method": f.method, "connectivity": f.connectivity,
-                      "h": f.h if f.mode in ("h_maxima", "h_minima") else None}
-            log(f"{i}: reconstruction mode={f.mode} method={f.method} "
-                f"connectivity={f.connectivity}"
-                + (f" h={f.h}" if params["h"] is not None else "")
-                + f" {src} ({info.data_type} {list(info.shape)})"
-                + (f" marker {marker}" if marker is not None else "") + f" -> {dst}")
-        else:
-            params = {"stride": list(f.stride), "discrete": bool(step.get("discrete", False))}
-            log(f"{i}: downsample stride={params['stride']} discrete={params['discrete']} "
-                f"{src} ({info.data_type} {list(info.shape)}) -> {dst}")
-        params.update(data_type=step.get("data_type"), encoding=enc, chunk_limit=limit)
-
-        def whole_step(dev):  # the filters whose rows cannot be split: their own store function
-            if name == "connected_components":
-                return S.connected_components(src, dst, params["connectivity"],
-                                              data_type=params["data_type"], device=dev,
-                                              encoding=enc)
-            if name == "distance_transform":
-                return S.distance_transform(src, dst, params["spacing"], params["squared"],
-                                            data_type=params["data_type"], device=dev,
-                                            encoding=enc)
-            if name == "label_size_filter":
-                return S.label_size_filter(src, dst, params["min_size"], params["max_size"],
-                                           params["relabel"], data_type=params["data_type"],
-                                           device=dev, encoding=enc)
-            if name == "reconstruction":
-                return S.reconstruction(src, dst, params["marker"],
-                                        params["method"] if params["marker"] else "dilation",
-                                        params["connectivity"], params["mode"], params["h"],
-                                        data_type=params["data_type"], device=dev, encoding=enc)
-            return S.summed_area_table(src, dst, data_type=params["data_type"], device=dev,
-                                       encoding=enc, chunk_limit=limit)
-
-        if gpus > 1 and not rows_splittable(name):
-            dev0 = (gpu_devices or [0])[0]
-            log(f"   {name}: chunk rows depend on each other in order; one process on device "
-                f"{dev0}, not {gpus}")
-            st = whole_step(dev0)
-        elif gpus > 1:
+        params = kind.params(f, step) if kind.params else {}
+        text = kind.text(params)
+        log(f"{i}: {name}{' ' + text if text else ''} {src} ({info.data_type} "
+            f"{list(info.shape)}){kind.after(params) if kind.after else ''} -> {dst}")
+        params.update(data_type=step.get("data_type"), encoding=encoding_of(step),
+                      chunk_limit=limit)
+        if gpus > 1 and kind.rows:
+            # the parent creates the output: with the type and fill value of the filter's rule
+            # (equal: bool, fill value false)
+            params["encoding"] = step_encoding(step, info.data_type)
             st = run_rows_parallel(name, src, dst, params, out_shape, gpus, 0,
                                    devices=gpu_devices)
-        elif name == "guided_filter":
-            st = S.guided_filter(src, dst, params["epsilon"], params["radius"],
-                                 data_type=params["data_type"], device=device,
-                                 encoding=enc, chunk_limit=limit)
-        elif name == "gaussian":
-            st = S.gaussian(src, dst, params["sigma"], params["kernel_half_size"],
-                            data_type=params["data_type"], device=device, encoding=enc,
-                            chunk_limit=limit)
-        elif not rows_splittable(name):
-            st = whole_step(device)
-        elif name in RANK:
-            st = S.rank_filter(src, dst, name, params["kernel_half_size"],
-                               data_type=params["data_type"], device=device, encoding=enc,
-                               chunk_limit=limit)
-        elif name in POINTWISE:
-            st = _store_pointwise(name, src, dst, params["args"], data_type=params["data_type"],
-                                  device=device, encoding=enc, chunk_limit=limit)
-        elif name == "arithmetic":
-            st = S.arithmetic(src, params["other"], dst, params["operator"],
-                              data_type=params["data_type"], device=device, encoding=enc,
-                              chunk_limit=limit)
         else:
-            st = S.downsample(src, dst, params["stride"], discrete=params["discrete"],
-                              data_type=params["data_type"], device=device, encoding=enc,
-                              chunk_limit=limit)
-        if "components" in st:
-            log(f"   {st['components']} components")
-        if "rounds" in st:
-            log(f"   {st['rounds']} rounds")
+            dev = device
+            if gpus > 1:
+                dev = (gpu_devices or [0])[0]
+                log(f"   {name}: chunk rows depend on each other in order; one process on device "
+                    f"{dev}, not {gpus}")
+            st = kind.store(src, dst, params, data_type=params["data_type"], device=dev,
+                            encoding=params["encoding"], chunk_limit=limit)
+        if kind.reports in st:
+            log(f"   {st[kind.reports]} {kind.reports}")
         out = S.open_array(dst)
         log(f"   -> {out.data_type} {list(out.shape)} in {st['wall_s']:.2f}s "
             f"(rw:{st['decode_s']:.2f}/{st['encode_s']:.2f} p:{st['kernel_s']:.3f})")
         if stats:
             log(json.dumps({"step": i, "filter": name, **st}))
         return st
+
 
     for step in steps:
         name = step.get("filter")
@@ -1144,21 +1102,14 @@ def run(steps: list, exists: str = "erase", tmp: str | None = None,
                                    f"(supported: {', '.join(ON_PATH)})")
     written = set()  # the temporaries that the steps so far write
     for step in steps:
-        if step.get("filter") in BINARY:
-            other = arithmetic_args(step)[1]
-            if isinstance(other, str) and other.startswith("$") and other not in written:
-                raise _abi.InvalidParameters(
-                    _abi.ERR_INVALID_PARAMETERS,
-                    f"arithmetic: other {other} is not the output of an earlier step")
-        if step.get("filter") == "reconstruction":
-            marker = reconstruction_of(step)[1]
-            if isinstance(marker, str) and marker.startswith("$") and marker not in written:
-                raise _abi.InvalidParameters(
-                    _abi.ERR_INVALID_PARAMETERS,
-                    f"reconstruction: marker {marker} is not the output of an earlier step")
-        out = step.get("output")
-        if isinstance(out, str) and out.startswith("$"):
-            written.add(out)
+        kind = STEP_KINDS[step["filter"]]
+        if kind.second is not None:
+            key, value_of = kind.second
+            ref = value_of(step)
+            if _is_named_temp(ref) and ref not in written:
+                raise _invalid(f"{kind.name}: {key} {ref} is not the output of an earlier step")
+        if _is_named_temp(step.get("output")):
+            written.add(step["output"])
     chains = dict(plan_chains(steps)) if device_chain and _device_ok(device) else {}
     t_all = time.perf_counter()
     if sys.stderr.isatty():
