@@ -587,6 +587,49 @@ int zt_reconstruction_apply_array(zt_ctx* ctx, int dtype, const void* mask, cons
                                   int marker_mode, double h, void* out, const int64_t* shape,
                                   int ndim, int connectivity, int method, uint64_t* rounds);
 
+/* ---- seeded watershed (an extension: the reference has no such filter) ------------------------- */
+
+/* The marker-controlled watershed of a relief from the non-zero elements of a seeds array of the
+ * same shape. The relief is compared only through the rank filters' total order (above), with the
+ * keys complemented when `descending` (a distance map flooded from its maxima); labels are carried
+ * as storage bits and never computed on. The domain D is every element, or with `foreground_only`
+ * every element whose relief is not zero by the labelling's rule; elements outside D get 0, are
+ * never crossed, and a seed there is ignored. Neighbours are reconstruction's. (1) c[p] is the
+ * least, over paths in D from a seed to p, of the greatest key on the path. (2) d[p] is 0 at seeds
+ * and where a D-neighbour has a smaller c, else 1 + the least d over D-neighbours of equal c; no d
+ * exists exactly where no seed is connected to p in D, and such elements get 0. (3) The parent of
+ * p is p at a seed; for d = 0 the D-neighbour of least (c, linear C index) among those with a
+ * smaller c; for d > 0 the neighbour of least linear index with equal c and d one less.
+ * (4) labels[p] = seeds[root of p]. The result is unique. Semantics, kernels and the termination
+ * argument: DESIGN.md §3.18. */
+/* An extension. A relief of any of the 13 types and seeds of one of the 8 integer types; anything
+ * else is ZT_ERR_UNSUPPORTED_DATA_TYPE. */
+int zt_watershed_is_compatible(int dtype_relief, int dtype_seeds);
+/* An extension. Device bytes of one call: inputs + output + scratch = n * size(relief) +
+ * 2 * n * size(seeds) + the scratch, every part of it rounded up to 16 bytes: two working arrays
+ * of n * size(relief) for the pass values, a third for the relief copy with `foreground_only`,
+ * two arrays of 4 n bytes (the plateau distances, then the parents), and 64 bytes of flag words.
+ * 0 for an array with a zero extent. What the call refuses for the connectivity, the rank or the
+ * size (below) is ZT_ERR_INVALID_PARAMETERS here too. */
+int zt_watershed_memory(int dtype_relief, int dtype_seeds, const int64_t* shape, int ndim,
+                        int connectivity, int foreground_only, uint64_t* bytes);
+/* An extension. The watershed of the whole C-order device arrays `relief` and `seeds`
+ * (shape[ndim], element alignment) into `out` (the seeds' type, not overlapping them) on the
+ * context's stream. connectivity outside [1, ndim], a rank above 3 with an axis in front of the
+ * innermost three whose extent is not 1, 2^32 - 1 elements or more, or more than 2^31 - 1 tiles
+ * are ZT_ERR_INVALID_PARAMETERS, before anything is written. Pass values are reconstruction's
+ * rounds, distances rounds of the same tile, jumps P' = P[P]; all are launched ZT_REC_BATCH at a
+ * time with one flag word each, the call synchronises the stream once per batch, and a phase stops
+ * at its first round that changed nothing. rounds (may be NULL) receives the pass rounds, the
+ * distance rounds and the jumps, each counting that last round. ZT_REC_TILE_SWEEPS=N caps the
+ * sweeps of a tile per round in both tiled phases. More than n + 1 pass or distance rounds or
+ * ceil(log2 n) + 2 jumps are ZT_ERR_OTHER; a refused scratch allocation is ZT_ERR_OUT_OF_MEMORY.
+ * A zero extent is a no-op with 0 rounds. There is no per-chunk form. */
+int zt_watershed_apply_array(zt_ctx* ctx, int dtype_relief, const void* relief, int dtype_seeds,
+                             const void* seeds, void* out, const int64_t* shape, int ndim,
+                             int connectivity, int descending, int foreground_only,
+                             int64_t rounds[3]);
+
 /* ---- zarrs_info reductions (src/info/range.rs, src/info/histogram.rs) ------------------------ */
 
 /* The 12 numeric types; ZT_BOOL is ZT_ERR_UNSUPPORTED_DATA_TYPE (the reference reaches

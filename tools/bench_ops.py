@@ -46,6 +46,11 @@ the Reencode uint8 -> uint32 cast; rounds, ms per call and ms per round against 
 floor of a round (two reads and one write per element); with scipy installed,
 scipy.ndimage.binary_fill_holes on the host fills the same masks at `--rec-scipy-size`^3 (default
 256; `--no-scipy` skips it); `--rec-once` calls every case once and nothing else.
+`--only watershed`: the seeded watershed (watershed.hip) on 1024^3: the uint32 squared distance map
+of the synth_u16 > q0.7 volume flooded from its maxima inside the foreground, seeded with its
+labelled h-maxima, alternated with the Reconstruction h_maxima(1) call and the connected_components
+call on the same volume; the three round counts, ms per call and the streaming floor of the phases
+launched.
 
 Algorithmic bytes: pyramid = level 0 read once + every level written once (2 B per u16
 element; the fused launches never read an intermediate level back); Gaussian = 4 B read + 4 B written per voxel (the separable passes' intermediates are
@@ -1251,6 +1256,104 @@ def bench_reconstruction(n, rounds=3, window_s=0.5, scipy_size=256, once=False):
     return res
 
 
+def bench_watershed(n, rounds=3, window_s=0.5):
+    """The seeded watershed (watershed.hip) on n^3 device arrays: the relief is the uint32 squared
+    distance map of the synth_u16 > q0.7 volume, flooded from its maxima (descending) inside the
+    foreground; the seeds are the labelled h-maxima (h = 1) of that map (Reconstruction, then
+    ConnectedComponents of the elements the reconstruction lowered). Alternated in one run with
+    two yardsticks of unchanged code on the same volume: the Reconstruction h_maxima(1) call and
+    the connected_components call (connectivity 1). Windows of at least window_s after a warm-up,
+    `rounds` of each, medians. Every call synchronises the stream once per batch of rounds; those
+    waits are inside the windows. Reported: the three round counts, ms per call, and the streaming
+    floor of the phases the call launches (reads plus writes at HBM_PEAK_GBS)."""
+    import math
+    import torch
+    import zarrs_tools_amd as zt
+    ctx = zt.default_context(0)
+    stream = torch.cuda.current_stream()
+    chunk = (32, 32, 32)
+    shape, total = (n, n, n), n ** 3
+    u16 = zt.synth_u16(shape)
+    sample = u16.reshape(-1)[:: max(1, total // (1 << 20))].to(torch.float32)
+    level = float(torch.quantile(sample, 0.7))
+    blobs = (u16.to(torch.float32) > level).to(torch.uint8)
+    del u16
+
+    def arr(t, dtype):
+        return zt.DeviceArray(t, chunk, dtype)
+
+    d2 = torch.empty(shape, dtype=torch.uint32, device="cuda")
+    zt.DistanceTransform(None, True).apply(arr(blobs, "uint8"), arr(d2, "uint32"), ctx=ctx)
+    out32 = torch.empty(shape, dtype=torch.uint32, device="cuda")
+    hmax = zt.Reconstruction(mode="h_maxima", h=1.0)
+    cc = zt.ConnectedComponents(1)
+    hmax.apply(arr(d2, "uint32"), arr(out32, "uint32"), ctx=ctx)
+    ctx.synchronize()
+    # the h-maxima: where the reconstruction of d2 - 1 under d2 stays below d2
+    maxima = (d2.view(torch.int32) != out32.view(torch.int32)).to(torch.uint8)
+    seeds = torch.empty(shape, dtype=torch.uint32, device="cuda")
+    n_seeds = int(cc.apply(arr(maxima, "uint8"), arr(seeds, "uint32"), ctx=ctx))
+    ctx.synchronize()
+    ctx.release_scratch()
+    del maxima
+    labels = torch.empty(shape, dtype=torch.uint32, device="cuda")
+    ws = zt.Watershed(1, descending=True, foreground_only=True)
+    ops = {
+        "h_maxima_1_c1": lambda: hmax.apply(arr(d2, "uint32"), arr(out32, "uint32"), ctx=ctx),
+        "connected_components_c1": lambda: cc.apply(arr(blobs, "uint8"), arr(out32, "uint32"),
+                                                    ctx=ctx),
+        "watershed_c1": lambda: ws.apply(arr(d2, "uint32"), arr(seeds, "uint32"),
+                                         arr(labels, "uint32"), ctx=ctx),
+    }
+    t0 = time.perf_counter()
+    counts = tuple(ops["watershed_c1"]())
+    ctx.synchronize()
+    first_s = round(time.perf_counter() - t0, 4)
+    h_rounds = int(ops["h_maxima_1_c1"]())
+    labelled = int((labels.view(torch.int32) != 0).sum())
+    foreground = int(blobs.sum())
+    reps = {}
+    for k, fn in ops.items():  # warm-up, then calls per window until it lasts window_s
+        r = 1
+        while True:
+            t = timed(fn, stream, r)
+            if t * r >= window_s * 1e3:
+                break
+            r = math.ceil(window_s * 1e3 / t * 1.05) + 1
+        reps[k] = r
+    ms = {k: [] for k in ops}
+    for _ in range(rounds):
+        for k, fn in ops.items():
+            ms[k].append(timed(fn, stream, reps[k]))
+    res = {"op": "watershed (device-resident)",
+           "config": {"shape": [n] * 3, "rounds": rounds, "window_s": window_s,
+                      "relief": "uint32 squared distance of synth_u16 > q0.7", "descending": True,
+                      "foreground_only": True, "connectivity": 1, "seeds": n_seeds,
+                      "tile_sweeps": os.environ.get("ZT_REC_TILE_SWEEPS", "default")},
+           "foreground": foreground, "labelled": labelled, "first_call_s": first_s, "ops": {}}
+    for k in ops:
+        v = sorted(ms[k])
+        med = v[len(v) // 2]
+        res["ops"][k] = {"ms": round(med, 4), "ms_min": round(v[0], 4), "ms_max": round(v[-1], 4),
+                         "spread": round((v[-1] - v[0]) / med, 4), "calls_per_window": reps[k]}
+    res["ops"]["h_maxima_1_c1"]["rounds_of_the_call"] = h_rounds
+    # bytes per element of the phases launched, 4-byte relief, seeds and indices: init reads the
+    # relief and the seeds and writes J0, the relief copy and d (20); a pass round and a distance
+    # round read two arrays and write one (12); the parents read c, d and the seeds and write one
+    # (16); a jump reads P, gathers P[P] and writes (12); the labels read the roots, gather the
+    # seeds and write (12)
+    per_elem = 20 + 12 * counts[0] + 12 * counts[1] + 16 + 12 * counts[2] + 12
+    floor = total * per_elem / (HBM_PEAK_GBS * 1e9) * 1e3
+    w = res["ops"]["watershed_c1"]
+    w.update({"pass_rounds": counts[0], "distance_rounds": counts[1], "jumps": counts[2],
+              "floor_bytes_per_element": per_elem, "floor_ms": round(floor, 3),
+              "over_floor": round(w["ms"] / floor, 2),
+              "ratio_to_h_maxima": round(w["ms"] / res["ops"]["h_maxima_1_c1"]["ms"], 2),
+              "ratio_to_connected_components": round(
+                  w["ms"] / res["ops"]["connected_components_c1"]["ms"], 2)})
+    return res
+
+
 def bench_guided4d(shape, chunk, radius, reps):
     """Config T per GPU: a (T, Z, Y, X) f32 time-series share, chunks
     (4, 256, 256, 256), eps 2500. 4-D arrays take the separable per-axis path."""
@@ -1425,6 +1528,8 @@ def main():
         print(json.dumps(bench_reconstruction(
             a.gaussian_size, scipy_size=0 if a.no_scipy else a.rec_scipy_size,
             once=a.rec_once)), flush=True)
+    if "watershed" in only:  # with h_maxima and the labelling of the same volume, alternated
+        print(json.dumps(bench_watershed(a.gaussian_size)), flush=True)
 
 
 if __name__ == "__main__":

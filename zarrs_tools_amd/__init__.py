@@ -41,6 +41,7 @@ from .filter import (  # noqa: E402
     ReplaceValue,
     Rescale,
     SummedAreaTable,
+    Watershed,
     combine_compares,
     combine_histograms,
     combine_label_statistics,
@@ -76,4 +77,5 @@ __all__ = [
     "LabelStatistics", "LabelSizeFilter", "combine_label_statistics", "label_statistics",
     "label_size_filter",
     "Reconstruction",
+    "Watershed",
 ]

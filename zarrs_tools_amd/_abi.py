@@ -275,6 +275,10 @@ def lib() -> ctypes.CDLL:
         "zt_reconstruction_memory": ([c_int, c_int, i64p, c_int, u64p], c_int),
         "zt_reconstruction_apply_array": ([vp, c_int, vp, vp, c_int, ctypes.c_double, vp, i64p,
                                            c_int, c_int, c_int, u64p], c_int),
+        "zt_watershed_is_compatible": ([c_int, c_int], c_int),
+        "zt_watershed_memory": ([c_int, c_int, i64p, c_int, c_int, c_int, u64p], c_int),
+        "zt_watershed_apply_array": ([vp, c_int, vp, c_int, vp, vp, i64p, c_int, c_int, c_int,
+                                      c_int, i64p], c_int),
         "zt_range_is_compatible": ([c_int], c_int),
         "zt_histogram_is_compatible": ([c_int], c_int),
         "zt_range_init": ([vp, vp], c_int),

@@ -2133,6 +2133,169 @@ int zt_reconstruction_apply_array(zt_ctx* ctx, int dtype, const void* mask, cons
     return ZT_OK;
 }
 
+// ---- seeded watershed (an extension; watershed.hip) ---------------------------------------------
+
+namespace {
+
+// what zt_watershed_memory and zt_watershed_apply_array refuse alike; n = 0 passes
+int ws_check(const int64_t* shape, int ndim, int connectivity, zt::RecGeom* geom) {
+    if (connectivity < 1 || connectivity > ndim)
+        return fail(ZT_ERR_INVALID_PARAMETERS, "watershed: connectivity %d not in [1, %d]",
+                    connectivity, ndim);
+    const int64_t n = numel(shape, ndim);
+    if (n == 0) return ZT_OK;
+    if (!zt::rec_geom(shape, ndim, geom))
+        return fail(ZT_ERR_INVALID_PARAMETERS,
+                    "watershed: rank %d is supported only when every axis in front of the "
+                    "innermost three has extent 1", ndim);
+    if (n > zt::kWsMaxElems)
+        return fail(ZT_ERR_INVALID_PARAMETERS, "watershed: %lld elements are more than %lld",
+                    (long long)n, (long long)zt::kWsMaxElems);
+    if (zt::rec_tiles(*geom) > 0x7FFFFFFFll)
+        return fail(ZT_ERR_INVALID_PARAMETERS,
+                    "watershed: %lld tiles are more than one launch holds",
+                    (long long)zt::rec_tiles(*geom));
+    return ZT_OK;
+}
+
+// Rounds in batches of kRecBatch, each with its own flag word, until the first that raised none:
+// `launch(r, flag, prev)` enqueues round r. *count = the rounds up to and including that one;
+// more than `cap` of them is ZT_ERR_OTHER.
+extern "C++" {
+template <typename Launch>
+int ws_rounds(zt_ctx* ctx, uint32_t* flags, uint64_t cap, const char* what, int64_t* count,
+              Launch launch) {
+    uint64_t done = 0;
+    for (;;) {
+        ZT_HIP(hipMemsetAsync(flags, 0, zt::kRecBatch * sizeof(uint32_t), ctx->cur));
+        for (int k = 0; k < zt::kRecBatch; ++k) {
+            const hipError_t e = launch(done + k, flags + k, k ? flags + k - 1 : nullptr);
+            if (e != hipSuccess) return hip_fail(e, what);
+        }
+        uint32_t host[zt::kRecBatch];
+        ZT_HIP(hipMemcpyAsync(host, flags, sizeof host, hipMemcpyDeviceToHost, ctx->cur));
+        ZT_HIP(hipStreamSynchronize(ctx->cur));
+        for (int k = 0; k < zt::kRecBatch; ++k)
+            if (host[k] == 0) {
+                *count = (int64_t)(done + k + 1);
+                return ZT_OK;
+            }
+        done += zt::kRecBatch;
+        if (done > cap)
+            return fail(ZT_ERR_OTHER, "watershed: %s: no fixed point after %llu rounds (cap %llu)",
+                        what, (unsigned long long)done, (unsigned long long)cap);
+    }
+}
+}  // extern "C++"
+
+}  // namespace
+
+int zt_watershed_is_compatible(int dtype_relief, int dtype_seeds) {
+    for (int d : {dtype_relief, dtype_seeds})
+        if (!valid_dtype(d))
+            return fail(ZT_ERR_UNSUPPORTED_DATA_TYPE, "Unsupported data type code %d", d);
+    if (cc_label_max(dtype_seeds) == 0)
+        return fail(ZT_ERR_UNSUPPORTED_DATA_TYPE,
+                    "watershed: seeds and labels need an integer type, not %s",
+                    dtype_name(dtype_seeds));
+    return ZT_OK;
+}
+
+int zt_watershed_memory(int dtype_relief, int dtype_seeds, const int64_t* shape, int ndim,
+                        int connectivity, int foreground_only, uint64_t* bytes) {
+    if (int rc = zt_watershed_is_compatible(dtype_relief, dtype_seeds)) return rc;
+    if (int rc = check_shape(shape, ndim, "shape")) return rc;
+    if (!bytes) return fail(ZT_ERR_INVALID_PARAMETERS, "null pointer");
+    zt::RecGeom geom;
+    if (int rc = ws_check(shape, ndim, connectivity, &geom)) return rc;
+    const int64_t n = numel(shape, ndim);
+    const int esz = (int)zt::dtype_size(dtype_relief), ssz = (int)zt::dtype_size(dtype_seeds);
+    // relief, seeds, output, scratch
+    *bytes = n == 0 ? 0
+                    : (uint64_t)n * esz + 2 * (uint64_t)n * ssz +
+                          zt::ws_scratch_bytes(n, esz, foreground_only != 0);
+    return ZT_OK;
+}
+
+int zt_watershed_apply_array(zt_ctx* ctx, int dtype_relief, const void* relief, int dtype_seeds,
+                             const void* seeds, void* out, const int64_t* shape, int ndim,
+                             int connectivity, int descending, int foreground_only,
+                             int64_t rounds[3]) {
+    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = zt_watershed_is_compatible(dtype_relief, dtype_seeds)) return rc;
+    if (int rc = check_shape(shape, ndim, "shape")) return rc;
+    zt::RecGeom geom;
+    if (int rc = ws_check(shape, ndim, connectivity, &geom)) return rc;
+    int64_t counts[3] = {0, 0, 0};
+    if (rounds) rounds[0] = rounds[1] = rounds[2] = 0;
+    const int64_t n = numel(shape, ndim);
+    if (n == 0) return ZT_OK;
+    if (!relief || !seeds || !out) return fail(ZT_ERR_INVALID_PARAMETERS, "null data pointer");
+    if (relief == out || seeds == out)
+        return fail(ZT_ERR_INVALID_PARAMETERS, "input and output must differ");
+    const int esz = (int)zt::dtype_size(dtype_relief), ssz = (int)zt::dtype_size(dtype_seeds);
+    if (((uintptr_t)relief % esz) != 0 || ((uintptr_t)seeds % ssz) != 0 ||
+        ((uintptr_t)out % ssz) != 0)
+        return fail(ZT_ERR_INVALID_PARAMETERS, "data pointers must be element aligned");
+    const bool desc = descending != 0, fg = foreground_only != 0;
+    const int sweeps = zt::rec_tile_sweeps();
+    DeviceGuard guard(ctx->device);
+    const uint64_t scratch_bytes = zt::ws_scratch_bytes(n, esz, fg);
+    if (int rc = ctx->ensure_scratch((size_t)scratch_bytes)) return rc;
+    if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev0, ctx->cur));
+    // the scratch: c[0], c[1], (the relief copy,) d[0], d[1], the flag words
+    uint8_t* at = static_cast<uint8_t*>(ctx->scratch);
+    const uint64_t cbytes = zt::ws_pad16((uint64_t)n * esz), dbytes = zt::ws_pad16((uint64_t)n * 4);
+    void* c[2] = {at, at + cbytes};
+    at += 2 * cbytes;
+    void* domain = fg ? at : nullptr;
+    if (fg) at += cbytes;
+    uint32_t* d[2] = {reinterpret_cast<uint32_t*>(at), reinterpret_cast<uint32_t*>(at + dbytes)};
+    uint32_t* flags = reinterpret_cast<uint32_t*>(at + 2 * dbytes);
+    hipStream_t s = ctx->cur;
+    hipError_t e = zt::launch_ws_init(relief, dtype_relief, seeds, dtype_seeds, c[0], domain, d[0],
+                                      n, desc, s);
+    if (e != hipSuccess) return hip_fail(e, "watershed init launch");
+    // 1. pass values: the reconstruction of J0 under the relief (by erosion; flooding from the
+    // maxima is the erosion on complemented keys, which is the dilation). At most n + 1 rounds
+    // (DESIGN.md §3.16); once a round has changed nothing c[0] and c[1] are equal.
+    const void* under = fg ? domain : relief;
+    if (int rc = ws_rounds(ctx, flags, (uint64_t)n, "pass value rounds", &counts[0],
+                           [&](uint64_t r, uint32_t* flag, const uint32_t* prev) {
+                               return zt::launch_rec_round(c[r % 2], under, c[(r + 1) % 2],
+                                                           dtype_relief, geom, connectivity, !desc,
+                                                           sweeps, flag, prev, s);
+                           }))
+        return rc;
+    // 2. plateau distances, at most n + 1 rounds; afterwards d[0] and d[1] are equal
+    if (int rc = ws_rounds(ctx, flags, (uint64_t)n, "distance rounds", &counts[1],
+                           [&](uint64_t r, uint32_t* flag, const uint32_t* prev) {
+                               return zt::launch_ws_dist_round(c[0], dtype_relief, d[r % 2],
+                                                               d[(r + 1) % 2], geom, connectivity,
+                                                               desc, sweeps, flag, prev, s);
+                           }))
+        return rc;
+    // 3. parents, from d[0] into d[1]; then the jumps alternate between the two d arrays, the
+    // distances being done with
+    e = zt::launch_ws_parent(c[0], dtype_relief, d[0], seeds, dtype_seeds, d[1], geom,
+                             connectivity, desc, s);
+    if (e != hipSuccess) return hip_fail(e, "watershed parent launch");
+    uint32_t* p[2] = {d[1], d[0]};
+    if (int rc = ws_rounds(ctx, flags, (uint64_t)zt::ws_jump_cap(n), "jumps", &counts[2],
+                           [&](uint64_t r, uint32_t* flag, const uint32_t* prev) {
+                               return zt::launch_ws_jump(p[r % 2], p[(r + 1) % 2], n, flag, prev,
+                                                         s);
+                           }))
+        return rc;
+    // 4. the round that changed nothing copied its input: both arrays hold the roots
+    e = zt::launch_ws_gather(p[0], seeds, dtype_seeds, out, n, s);
+    if (e != hipSuccess) return hip_fail(e, "watershed gather launch");
+    if (ctx->timed) ZT_HIP(hipEventRecord(ctx->ev1, ctx->cur));
+    if (rounds)
+        for (int k = 0; k < 3; ++k) rounds[k] = counts[k];
+    return ZT_OK;
+}
+
 // ---- zarrs_info reductions (range.rs, histogram.rs) --------------------------------------------
 
 namespace {

@@ -371,6 +371,44 @@ hipError_t launch_rec_round(const void* src, const void* mask, void* dst, int dt
                             const RecGeom& geom, int connectivity, bool erosion, int sweeps,
                             uint32_t* flag, const uint32_t* prev, hipStream_t s);
 
+// Seeded watershed (watershed.hip; an extension, no reference filter) of a
+// contiguous C-order relief and a seeds array of an integer type, seen as reconstruction sees its
+// arrays (RecGeom, the same tile, rec_tile_sweeps(), batches of kRecBatch). Scratch
+// (ws_scratch_bytes), every part padded to 16 bytes: the two working arrays of the pass values
+// (the relief's type), the relief with the greatest flood key outside the domain (the relief's
+// type; only with `foreground_only`), two arrays of n uint32_t (the plateau distances, then the
+// parents) and the flag words. launch_ws_init writes J0 into `j0`, the relief copy into `domain`
+// (NULL: the domain is everything) and the first distances into `d0`; launch_ws_dist_round writes
+// one round of `src` into `dst` from the pass values `c`, with the flag protocol of
+// launch_rec_round; launch_ws_parent writes the parents from the final c and d; launch_ws_jump
+// writes dst = src[src] and ORs 1 into *flag when an entry changed; launch_ws_gather writes
+// labels[i] = seeds[root[i]], or 0. Everything runs on `s`; nothing synchronises.
+constexpr int64_t kWsMaxElems = 0xFFFFFFFEll;  // n < 2^32 - 1: two index values are marks
+inline uint64_t ws_pad16(uint64_t bytes) { return (bytes + 15) & ~(uint64_t)15; }
+inline uint64_t ws_scratch_bytes(int64_t n, int esz, bool foreground_only) {
+    return (foreground_only ? 3 : 2) * ws_pad16((uint64_t)n * (uint64_t)esz) +
+           2 * ws_pad16((uint64_t)n * 4) + kRecTail;
+}
+// jump rounds of n elements: ceil(log2 n) + 2
+inline int ws_jump_cap(int64_t n) {
+    int bits = 0;
+    while (((int64_t)1 << bits) < n) ++bits;
+    return bits + 2;
+}
+hipError_t launch_ws_init(const void* relief, int dtype, const void* seeds, int dtype_seeds,
+                          void* j0, void* domain, uint32_t* d0, int64_t n, bool descending,
+                          hipStream_t s);
+hipError_t launch_ws_dist_round(const void* c, int dtype, const uint32_t* src, uint32_t* dst,
+                                const RecGeom& geom, int connectivity, bool descending, int sweeps,
+                                uint32_t* flag, const uint32_t* prev, hipStream_t s);
+hipError_t launch_ws_parent(const void* c, int dtype, const uint32_t* d, const void* seeds,
+                            int dtype_seeds, uint32_t* parent, const RecGeom& geom,
+                            int connectivity, bool descending, hipStream_t s);
+hipError_t launch_ws_jump(const uint32_t* src, uint32_t* dst, int64_t n, uint32_t* flag,
+                          const uint32_t* prev, hipStream_t s);
+hipError_t launch_ws_gather(const uint32_t* root, const void* seeds, int dtype_seeds, void* labels,
+                            int64_t n, hipStream_t s);
+
 // zarrs_info reductions (info.hip; src/info/range.rs, src/info/histogram.rs) over a contiguous
 // run of n elements of `dtype` (the 12 numeric types) at element alignment.
 // Range: `state` is two device u64 words (smallest key, largest key) that accumulate across

@@ -1963,6 +1963,99 @@ class Reconstruction:
         return self._run(x, dtype, marker, output.data, output.dtype, ctx)
 
 
+class Watershed:
+    """An extension with no counterpart in the reference: the marker-controlled
+    watershed. Every non-zero element of `seeds` (one of the 8 integer types, the relief's shape)
+    is a label, carried as storage bits; the result has the seeds' type. The relief, any of the 13
+    types, is compared only under the rank filters' total order, complemented with `descending` (a
+    distance map flooded from its maxima). The domain is every element, or with `foreground_only`
+    the non-zero elements of the relief (the labelling's rule); elements outside it get 0, are
+    never crossed, and a seed there is ignored. An element takes the label of the seed that
+    reaches it over the lowest pass; ties are decided by the distance on the plateau and then by
+    the least linear index, so the result is unique. Elements of the domain that no seed reaches
+    get 0. Neighbours are the labelling's. A whole-array operation: there is no per-chunk form."""
+
+    def __init__(self, connectivity: int = 1, descending: bool = False,
+                 foreground_only: bool = False):
+        self.connectivity = int(connectivity)
+        self.descending = bool(descending)
+        self.foreground_only = bool(foreground_only)
+        if self.connectivity < 1:
+            raise _invalid(f"watershed: connectivity {self.connectivity} not in [1, rank]")
+
+    def name(self) -> str:
+        return "watershed"
+
+    def check_connectivity(self, ndim: int) -> None:
+        """InvalidParameters unless 1 <= connectivity <= ndim."""
+        if not 1 <= self.connectivity <= int(ndim):
+            raise _invalid(f"watershed: connectivity {self.connectivity} not in "
+                           f"[1, {int(ndim)}]")
+
+    def is_compatible(self, dtype_relief: str, dtype_seeds: str) -> None:
+        """UnsupportedDataType unless the seeds (and so the labels) have an integer type."""
+        check(lib().zt_watershed_is_compatible(_info_dtype(dtype_relief),
+                                               _info_dtype(dtype_seeds)))
+
+    def memory(self, dtype_relief: str, dtype_seeds: str, shape) -> int:
+        """Device bytes of one call on arrays of `shape`: inputs + output + scratch."""
+        self.is_compatible(dtype_relief, dtype_seeds)
+        self.check_connectivity(len(shape))
+        out = ctypes.c_uint64()
+        check(lib().zt_watershed_memory(
+            _info_dtype(dtype_relief), _info_dtype(dtype_seeds), i64_array(shape), len(shape),
+            self.connectivity, int(self.foreground_only), ctypes.byref(out)))
+        return int(out.value)
+
+    def _run(self, x, dtype, seeds, out, dtype_out, ctx) -> tuple:
+        s, dtype_seeds = _info_run(seeds)
+        if tuple(s.shape) != tuple(x.shape):
+            raise _invalid(f"Array shapes do not match: {list(x.shape)} vs {list(s.shape)}")
+        if tuple(out.shape) != tuple(x.shape):
+            raise _invalid(f"Array shapes do not match: {list(x.shape)} vs {list(out.shape)}")
+        if s.device != x.device or x.device != out.device:
+            raise _invalid("watershed: the arrays are on different devices")
+        if not out.is_contiguous():
+            raise _invalid("watershed: the output must be contiguous")
+        self.is_compatible(dtype, dtype_seeds)
+        if dtype_out != dtype_seeds:
+            raise _abi.UnsupportedDataType(
+                _abi.ERR_UNSUPPORTED_DATA_TYPE,
+                f"watershed: the labels have the seeds' data type {dtype_seeds}, not {dtype_out}")
+        self.check_connectivity(x.dim())
+        ctx = ctx or default_context(x.device.index)
+        rounds = (ctypes.c_int64 * 3)()
+        check(lib().zt_watershed_apply_array(
+            ctx.handle, DTYPES[dtype], _ptr(x), DTYPES[dtype_seeds], _ptr(s), _ptr(out),
+            i64_array(x.shape), x.dim(), self.connectivity, int(self.descending),
+            int(self.foreground_only), rounds))
+        return tuple(int(r) for r in rounds)
+
+    def apply_ndarray(self, relief, seeds, ctx: Optional[Context] = None, out=None):
+        """The watershed on device tensors; returns (labels, rounds). labels is a new tensor of
+        the seeds' type, or `out` (contiguous, of that type, not overlapping the inputs); rounds is
+        (pass rounds, distance rounds, jumps), each counting the first round that changed
+        nothing. A bool or 16-bit float relief is named by a DeviceArray."""
+        x, dtype = _info_run(relief)
+        s, dtype_seeds = _info_run(seeds)
+        if out is None:
+            if tuple(s.shape) != tuple(x.shape):
+                raise _invalid(f"Array shapes do not match: {list(x.shape)} vs {list(s.shape)}")
+            out = _torch().empty(tuple(x.shape), dtype=s.dtype, device=x.device)
+            dtype_out = dtype_seeds
+        elif isinstance(out, DeviceArray):
+            out, dtype_out = out.data, out.dtype
+        else:
+            dtype_out = dtype_seeds if out.dtype == s.dtype else dtype_of(out)
+        return out, self._run(x, dtype, seeds, out, dtype_out, ctx)
+
+    def apply(self, relief: DeviceArray, seeds: DeviceArray, output: DeviceArray,
+              ctx: Optional[Context] = None) -> tuple:
+        """The filter's `apply` over device-resident arrays; returns the rounds."""
+        x, dtype = _info_run(relief)
+        return self._run(x, dtype, seeds, output.data, output.dtype, ctx)
+
+
 class Downsample:
     """downsample.rs:49-287 — `Downsample::new(stride, discrete, chunk_limit)`."""
 

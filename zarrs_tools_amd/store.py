@@ -790,6 +790,82 @@ def reconstruction(input_path, output_path, marker_path=None, method: str = "dil
     return st
 
 
+def watershed_output(seeds_data_type: str, data_type: Optional[str] = None, encoding=None):
+    """(output data type, encoding) of a watershed's output array: the seeds' type (an explicit
+    other type is UnsupportedDataType) and fill value 0 unless given."""
+    dt, enc = _typed_output(seeds_data_type, data_type, encoding)
+    if dt != seeds_data_type:
+        raise _abi.UnsupportedDataType(
+            _abi.ERR_UNSUPPORTED_DATA_TYPE,
+            f"watershed: the output has the seeds' data type {seeds_data_type}, not {dt}")
+    return dt, enc
+
+
+class SeedsStep:
+    """Watershed as a whole-array step drives it: the seeds are read into device memory after the
+    relief (their bytes are in `memory`) and released with the step."""
+
+    def __init__(self, filt, seeds_path, device: int, nthreads: int):
+        self.filt, self.seeds_path = filt, seeds_path
+        self.device, self.nthreads = device, nthreads
+
+    def memory(self, dtype_in, dtype_out, shape) -> int:
+        return self.filt.memory(dtype_in, dtype_out, shape)
+
+    def apply(self, input, output, ctx=None):
+        from . import filter as F
+        from .device_io import read_to_device
+        info = open_array(self.seeds_path)
+        seeds = read_to_device(self.seeds_path, self.device, self.nthreads)
+        return self.filt.apply(input, F.DeviceArray(seeds, info.chunk_shape, info.data_type),
+                               output, ctx=ctx)
+
+
+def watershed(input_path, seeds_path, output_path, connectivity: int = 1,
+              descending: bool = False, foreground_only: bool = False,
+              data_type: Optional[str] = None, device: int = 0, nthreads: int = 0,
+              encoding=None) -> dict:
+    """zarrs_watershed RELIEF SEEDS OUT [--connectivity C] [--descending] [--foreground-only]:
+    the marker-controlled watershed (filter.Watershed) of the relief at `input_path` from the
+    non-zero elements of the integer array at `seeds_path` (same shape; any chunk grid and
+    codecs). The output has the seeds' data type and fill value 0. A basin may span every chunk,
+    so the arrays are read into device memory, flooded there and the labels written once; there is
+    no store -> store path, and arrays that do not fit 80 % of the free device memory fail with
+    ZT_ERR_OUT_OF_MEMORY before anything is read. Returns the run stats and "rounds": (pass
+    rounds, distance rounds, jumps)."""
+    import time
+    from . import filter as F
+    t0 = time.perf_counter()
+    info = open_array(input_path)
+    sinfo = open_array(seeds_path)
+    filt = F.Watershed(connectivity, descending, foreground_only)
+    filt.is_compatible(info.data_type, sinfo.data_type)
+    dt, enc = watershed_output(sinfo.data_type, data_type, encoding)
+    if tuple(sinfo.shape) != tuple(info.shape):
+        raise _abi.InvalidParameters(
+            _abi.ERR_INVALID_PARAMETERS,
+            f"Array shapes do not match: {list(info.shape)} vs {list(sinfo.shape)}")
+    filt.check_connectivity(info.ndim)
+    no_fallback = ("watershed works on the whole array in device memory (a basin may span every "
+                   "chunk): there is no store -> store path to fall back to")
+    shape = [int(s) for s in info.shape]
+    if all(s > 0 for s in shape):
+        # the pinned pieces of the seeds' read, before anything is read (the relief's pieces and
+        # the output's rows are _whole_array_step's)
+        host_need = _pinned_read_bytes(shape, sinfo.chunk_shape,
+                                       NUMPY[sinfo.data_type]().itemsize)
+        host_budget = host_available_bytes() // 10 * 8
+        if host_need > host_budget:
+            _not_enough_memory(host_need, host_budget, PINNED_BUFFERS_NEED, no_fallback)
+    st, rounds = _whole_array_step(
+        input_path, output_path, info, SeedsStep(filt, seeds_path, device, nthreads), dt, enc,
+        device, nthreads, t0,
+        "relief, seeds, labels, the working arrays of the pass values and two index arrays",
+        no_fallback)
+    st["rounds"] = tuple(int(r) for r in rounds)
+    return st
+
+
 def label_statistics(labels_path, intensity_path=None, n_labels: Optional[int] = None,
                      device: int = 0, nthreads: int = 0) -> dict:
     """zarrs_info PATH label-statistics [--intensity PATH] [--n-labels K]: the per-label count,
