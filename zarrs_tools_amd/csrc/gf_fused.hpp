@@ -67,6 +67,17 @@
 #define GF_P5VPF 1  // r = 4, mode 1: P5's v loaded this many steps ahead (1 or 2; 2 VGPRs; 2 spills
                     // SGPRs and measured +4 % beside the two above)
 #endif
+#ifndef GF_V5LEAVE
+#define GF_V5LEAVE 1  // r = 4, mode 1: P5's v handed over in LDS (Vs) from the leaving stage-1 quad
+                      // that P12 consumed one barrier interval earlier, instead of loaded again
+                      // (0: load_p5v). With GF_P5OFFREG -1.9 % at 2048^3 on boxes where the
+                      // march takes 28.6 ms, neutral on one at 27.3 ms; each alone neutral
+                      // (profiles/gf_p5v_leave_ab.txt)
+#endif
+#ifndef GF_P5OFFREG
+#define GF_P5OFFREG 1  // r = 4, mode 1: P5's K5 store offsets computed once before the march and
+                       // held (0: compare, select, multiply and add per output every step)
+#endif
 #ifndef GF_WAVE_SKIP
 #define GF_WAVE_SKIP 1  // P4: idle waves branch around the phase
 #endif
@@ -481,6 +492,12 @@ __device__ __forceinline__ int opaque(int v) {
     return v;
 }
 
+// The same for a wave-uniform 64-bit value held in scalar registers.
+__device__ __forceinline__ int64_t opaque_s(int64_t v) {
+    __asm__ volatile("" : "+s"(v));
+    return v;
+}
+
 // A quad whose elements may lie partly outside the domain (edge tiles): element e is read at
 // off + e*size when bit e of mask is set, else reads 0 (kBadOff). Interior tiles use Quad::load.
 template <typename T>
@@ -512,7 +529,10 @@ __device__ __forceinline__ void store_quad_masked(const float (&v)[4], rsrc_t r,
 //       per lane and row, straight into registers)  +  P12(i+1) [z-window of v in registers,
 //       x-sums by DPP -> Hx]  +  P4(i) [x-sums of (a,b): Lab -> Hab]
 // with separate LDS buffers per hand-off (Hx, Lab, Hab), so each barrier interval holds
-// independent work from different slices. No global value is staged through LDS. The stage-1
+// independent work from different slices. No global value is staged through LDS, with one
+// exception at r = 4 in mode 1 (GF_V5LEAVE): P5's v is not loaded at all there. The slice P12(i+1)
+// subtracts as leaving is the slice P5(i) emits in the next C0, so the P12 lanes inside the
+// tile pass their leaving quad on through Vs (8 KB, one buffer). The stage-1
 // loads are 16-byte-per-lane quads (4 consecutive x) outside the masked edge mode: with one
 // dword per lane there, the kernel is bound by vector-memory instruction issue.
 // ---------------------------------------------------------------------------------------------
@@ -566,7 +586,19 @@ struct GFConfig {
     static constexpr int OFF_HX = 0, OFF_LAB = OFF_HX + SZ_HX;
     static constexpr int OFF_HAB = OFF_LAB + SZ_LAB;
     static constexpr int OFF_RCP = OFF_HAB + SZ_HAB;
-    static constexpr int LDS_BYTES = OFF_RCP + SZ_RCP;
+    // Vs (GF_V5LEAVE): the tile interior of the slice leaving the stage-1 z-window, TX x TY
+    // 4-byte values (f32, or the integers of an integer stage 1), P12 -> P5. Rows of TX = 64
+    // dwords: a P12 lane's ds_write_b128 covers 4 of the 32 banks and its group of 8 contiguous
+    // lanes lies in one row (32 consecutive dwords) or ends one row at dword 63 and starts the
+    // next at dword 0, so no two lanes of a group share a bank; P5's ds_read_b32 reads 64
+    // consecutive dwords per wave. No padding. The even-radius condition makes the tile's
+    // columns whole quads of the E2 row (quads R/2 .. R/2 + TX/4 - 1). Allocated for every mode
+    // of the r = 4 configuration (one LDS size per configuration), used by mode 1.
+    static constexpr bool V5L = GF_V5LEAVE && R4 && R % 2 == 0 && !P1RING;
+    static constexpr int PV = TX;
+    static constexpr int SZ_VS = V5L ? al(TY * PV * 4) : 0;
+    static constexpr int OFF_VS = OFF_RCP + SZ_RCP;
+    static constexpr int LDS_BYTES = OFF_VS + SZ_VS;
     // item -> thread placement: heavy phases on different waves (see C0 / C1)
     static constexpr int T3 = NT - N3;  // first thread of the P3 items (the top N3 threads)
     static_assert(TX * TY % NT == 0, "tile must divide evenly over the threads");
@@ -605,6 +637,8 @@ __global__ __launch_bounds__(NT) void gf3d_fused_kernel(GFParams p) {
     float2* const Lab = reinterpret_cast<float2*>(smem + C::OFF_LAB);
     float2* const Hab = reinterpret_cast<float2*>(smem + C::OFF_HAB);
     float* const rcp_tab = reinterpret_cast<float*>(smem + C::OFF_RCP);
+    SI* const Vs = reinterpret_cast<SI*>(smem + C::OFF_VS);  // GF_V5LEAVE only
+    static_assert(sizeof(SI) == 4, "Vs holds 4-byte stage-1 values");
     // Correctly rounded reciprocals of every possible window count, for div_by_count
     // (Markstein's correction needs RN(1/c) exactly). Published by the prologue's barrier.
     for (int c = threadIdx.x; c <= C::W3; c += NT) rcp_tab[c] = c > 0 ? 1.0f / (float)c : 0.0f;
@@ -697,6 +731,21 @@ __global__ __launch_bounds__(NT) void gf3d_fused_kernel(GFParams p) {
         q1mask[k] = m;
         q1off[k] = (EDGE ? valid : m == 0xF) ? (gy * sy + gx) * ESZ : kBadOff;
     }
+    // GF_V5LEAVE: where a P12 lane's leaving quad goes in Vs (element index): its place in the
+    // tile, or -1 for the lanes outside it (apron, idle lanes). A constant of the march in one
+    // register; the store's lane mask is its sign, compared every step (held as a mask it is an
+    // SGPR pair live through the march). Storing from every lane, the outside ones to a spare
+    // quad, measured the same to 0.2 ms slower (profiles/gf_p5v_leave_ab.txt).
+    constexpr bool V5LEAVE = C::V5L && MODE == 1;
+    int vs_dst[C::NQP1];
+#pragma unroll
+    for (int k = 0; k < (V5LEAVE ? C::NQP1 : 0); ++k) {
+        int row, cq;
+        const bool valid = p12_pos(tid0, k, row, cq);
+        const int ty = row - 2 * R, tq = cq - R / 2;
+        const bool in_tile = valid && (unsigned)ty < (unsigned)TY && (unsigned)tq < (unsigned)(TX / 4);
+        vs_dst[k] = opaque(in_tile ? ty * C::PV + 4 * tq : -1);
+    }
     auto load_quad = [&](rsrc_t r, int off, int mask, SI (&v)[4]) {
         if constexpr (EDGE) load_quad_masked<TIn>(r, off, mask, v);
         else Quad<TIn>::load(r, off, v);
@@ -765,12 +814,19 @@ __global__ __launch_bounds__(NT) void gf3d_fused_kernel(GFParams p) {
     constexpr bool R4M1 = C::R4 && MODE == 1;
     constexpr int PF = EDGE ? 1 : R4M1 ? GF_P1PFD_R4M1 : R == 4 ? GF_P1PFD : R <= 2 ? GF_P1PFD_R2 : 1;
     SI pa[PF][C::NQP1][EPL], ps[PF][C::NQP1][EPL];
+    // P5's v from the leaving stage-1 quad (GF_V5LEAVE): the slice that P12(i+1) subtracts in C1
+    // of step i is slice i-R, the slice P5(i) emits in C0 of step i+1, and the 80 x 48 apron of
+    // the P12 lanes contains the tile. The lanes whose quad lies in the tile store it to Vs; P5
+    // reads its K5 values from there: no second load of those values, no v5 registers, no
+    // descriptor or address arithmetic for that stream (V5LEAVE, above).
+    // P5's store offsets held in registers through the march (GF_P5OFFREG)
+    constexpr bool P5OFFREG = R4M1 && GF_P5OFFREG;
     // P3's and P5's v, loaded PF3 / PF5 steps ahead (buffer b feeds the unrolled steps k with
     // k % PF3 / PF5 == b). P3's two steps ahead at r = 4 in mode 1.
-    constexpr int PF3 = R4M1 ? GF_P3VPF : 1, PF5 = R4M1 ? GF_P5VPF : 1;
+    constexpr int PF3 = R4M1 ? GF_P3VPF : 1, PF5 = V5LEAVE ? 1 : R4M1 ? GF_P5VPF : 1;
     static_assert(PF <= 2 && PF3 <= 2 && PF5 <= 2, "the unroll covers one or two windows");
     float vc[PF3][C::K3];  // v of the next P3 slices at this thread's item (prefetched)
-    float v5[PF5][K5];     // v of the next P5 output slices at this thread's outputs
+    float v5[PF5][K5];     // v of the next P5 output slices at this thread's outputs (load_p5v)
 #pragma unroll
     for (int b = 0; b < PF5; ++b)
 #pragma unroll
@@ -829,6 +885,16 @@ __global__ __launch_bounds__(NT) void gf3d_fused_kernel(GFParams p) {
                 } else {
                     zv[k][e] = zv[k][e] - (SA)ps[b][k][e];  // leaving slice (0 outside the domain)
                 }
+            }
+            if constexpr (V5LEAVE) {
+                // the leaving quad of a lane inside the tile -> Vs, for the P5 of the next C0
+                // (one lane-masked 16-byte LDS store, which the four waves with no row in the
+                // tile skip; the values are what load_p5v would load: the same slice and range
+                // checks, the integers of an integer stage 1 as loaded)
+                typedef SI si4 __attribute__((ext_vector_type(4)));
+                if (vs_dst[k] >= 0)
+                    *reinterpret_cast<si4*>(Vs + vs_dst[k]) =
+                        (si4){ps[b][k][0], ps[b][k][1], ps[b][k][2], ps[b][k][3]};
             }
             constexpr int NB = C::NB;
             SA win[EPL * (2 * NB + 1)];  // lane items cq-NB .. cq+NB
@@ -1035,9 +1101,23 @@ __global__ __launch_bounds__(NT) void gf3d_fused_kernel(GFParams p) {
 #pragma unroll
         for (int j = 0; j < K5 + 2 * R; ++j) vin[j] = src[j * C::PB];
     };
-    auto do_p5 = [&](int tid, int zc, auto slot_c, auto vbc, const f2 (&vin)[K5 + 2 * R]) {
-        // y-window -> slice sums; z; out -> global
+    // P5's v: from Vs (issued with the Hab reads, ahead of the window arithmetic), converted as
+    // Buf<TIn>::load converts; or the registers load_p5v filled PF5 steps ago.
+    auto p5_v = [&](int tid, auto vbc, float (&vv)[K5]) {
         constexpr int vb = decltype(vbc)::value;  // prefetch buffer of this step's v
+        if constexpr (V5LEAVE) {
+            const SI* src = Vs + (tid / TX * K5) * C::PV + tid % TX;
+#pragma unroll
+            for (int j = 0; j < K5; ++j) vv[j] = (float)src[j * C::PV];
+        } else {
+#pragma unroll
+            for (int j = 0; j < K5; ++j) vv[j] = v5[vb][j];
+        }
+    };
+    int off5[K5];  // GF_P5OFFREG: P5's store offsets, constants of the march (set below)
+    auto do_p5 = [&](int tid, int zc, auto slot_c, const float (&vv)[K5],
+                     const f2 (&vin)[K5 + 2 * R]) {
+        // y-window -> slice sums; z; out -> global
         const int col5 = tid % TX, seg5 = tid / TX;
         f2 s2[K5];
         core_window_sums<R, K5>(vin, s2);
@@ -1083,12 +1163,26 @@ __global__ __launch_bounds__(NT) void gf3d_fused_kernel(GFParams p) {
         for (int j = 0; j < K5; ++j) {
             const f2 q = AB[j] * rc[j];
             const int oy = oyb + j;
-            const float o = __fadd_rn(__fmul_rn(v5[vb][j], q.x), q.y);  // v*=ma; v+=mb
-            const int off = (ox < ox_end && oy < oy_end)
-                                ? ((oy - p.oy0) * osy + (ox - p.ox0)) * OSZ : kBadOff;
-            Buf<TOut>::store(from_f32<TOut>(o), ro5, opaque(off));
+            const float o = __fadd_rn(__fmul_rn(vv[j], q.x), q.y);  // v*=ma; v+=mb
+            if constexpr (P5OFFREG) {
+                Buf<TOut>::store(from_f32<TOut>(o), ro5, off5[j]);
+            } else {
+                const int off = (ox < ox_end && oy < oy_end)
+                                    ? ((oy - p.oy0) * osy + (ox - p.ox0)) * OSZ : kBadOff;
+                Buf<TOut>::store(from_f32<TOut>(o), ro5, opaque(off));
+            }
         }
     };
+    if constexpr (P5OFFREG) {
+        // hidden from the optimiser once, here: the march sees K5 plain registers, so it neither
+        // recomputes the select per step nor turns it into a branch around the store (a second
+        // opaque() at the store would copy the register every step)
+        const int ox = x0 + tid0 % TX, oyb = y0 + tid0 / TX * K5;
+#pragma unroll
+        for (int j = 0; j < K5; ++j)
+            off5[j] = opaque((ox < ox_end && oyb + j < oy_end)
+                                 ? ((oyb + j - p.oy0) * osy + (ox - p.ox0)) * OSZ : kBadOff);
+    }
 
     // ---- v loaders: one element per access, lanes on consecutive x (coalesced rows) -------------
     // Every global access of the march below is unconditional, in the same order every step:
@@ -1098,6 +1192,7 @@ __global__ __launch_bounds__(NT) void gf3d_fused_kernel(GFParams p) {
     // kernel); straight-line, it waits for exactly the step-old load it needs.
     // Positions outside the domain either read 0 through the range check or read a neighbour
     // row's value that is never used (P3 zeroes its out-of-domain (a, b); P5's store drops).
+    // load_p5v is not called under GF_V5LEAVE (P5's v arrives through Vs, see do_p12 / p5_v).
     auto load_p3v = [&](auto bc, rsrc_t r) {
         constexpr int b = decltype(bc)::value;
         const int item = (int)threadIdx.x - C::T3;
@@ -1174,8 +1269,15 @@ __global__ __launch_bounds__(NT) void gf3d_fused_kernel(GFParams p) {
 
     // ---- slice streams: descriptors advanced by one slice per step (two 32-bit adds each)
     //      instead of rebuilt from z (a 64-bit multiply and range checks per descriptor) ------
-    // step i reads slice zb = i+1-R (leaving slice of P1(i+2), and v5), zb+R+1 = i+2 (P3's v)
-    // and zb+2R+1 = i+2+R (entering slice of P1(i+2)); it stores output slice zs = i-1-R.
+    // With one-step prefetch, step i reads slice zb = i+1-R (leaving slice of P12(i+2)), zb+R+PF3-1
+    // (P3's v, PF3 steps ahead) and zb+2R+1 = i+2+R (entering slice of P12(i+2)); two-step
+    // stage-1 prefetch reads one slice further on both. It stores output slice zs = i-1-R.
+    // P5's v: P12(i+1), in C1 of step i, consumes as leaving the quad of slice i-R under either
+    // prefetch depth (the depth only moves the load, not the use), and P5(i), in C0 of step i+1,
+    // emits slice i-R. GF_V5LEAVE hands that quad over in Vs, single-buffered: the barrier
+    // ending C1 publishes it and the barrier ending the next C0 frees it. The first P5 of a
+    // march reads what the prologue's P12 wrote (slice zc_begin-1-R) and emits nothing. Without
+    // the knob step i loads slice zb+PF5-2 for P5 again (load_p5v).
     const int64_t sstride = p.in_sz * ESZ, osstride = p.out_sz * OSZ;
     const int64_t off_a = (int64_t)(2 * R + 1) * sstride;
     int zb = zc_begin + 1 - R;
@@ -1230,17 +1332,19 @@ __global__ __launch_bounds__(NT) void gf3d_fused_kernel(GFParams p) {
             do_p3(tid, i, std::integral_constant<int, k % PF3>{}, vin3);
             if constexpr (GF_PRIO) __builtin_amdgcn_s_setprio(1);
             f2 vin5[K5 + 2 * R];
+            float vv5[K5];
             p5_load(tid, vin5);
-            do_p5(tid, i - 1, std::integral_constant<int, (k + W - 1) % W>{},
-                  std::integral_constant<int, k % PF5>{}, vin5);
+            p5_v(tid, std::integral_constant<int, k % PF5>{}, vv5);
+            do_p5(tid, i - 1, std::integral_constant<int, (k + W - 1) % W>{}, vv5, vin5);
             lds_barrier();
             if constexpr (GF_PRIO) __builtin_amdgcn_s_setprio(3);
             // C1: the loads of the next steps, P12(i+1), P4(i). Every wait here is for a load
             // issued a step ago or earlier.
             load_p3v(std::integral_constant<int, k % PF3>{},  // P3 slice i+PF3
                      rs_in(ob + (int64_t)(R + PF3 - 1) * sstride, zb + R + PF3 - 1));
-            load_p5v(std::integral_constant<int, k % PF5>{},  // P5 slice i-R+PF5-1
-                     rs_in(ob + (int64_t)(PF5 - 2) * sstride, zb + PF5 - 2));
+            if constexpr (!V5LEAVE)
+                load_p5v(std::integral_constant<int, k % PF5>{},  // P5 slice i-R+PF5-1
+                         rs_in(ob + (int64_t)(PF5 - 2) * sstride, zb + PF5 - 2));
             if constexpr (C::ORDER & 2) do_p4(tid);
             using BK = std::integral_constant<int, k % PF>;
             do_p12(tid, std::integral_constant<int, k % W>{}, BK{});
@@ -1255,6 +1359,13 @@ __global__ __launch_bounds__(NT) void gf3d_fused_kernel(GFParams p) {
             ob += sstride;
             ++zs;
             os += osstride;
+            if constexpr (V5LEAVE) {
+                // keep the two slice offsets running sums: otherwise the compiler rewrites them
+                // as base + k * stride with the 18 multiples of each stride hoisted out of the
+                // march, and spills 47 SGPRs to hold them
+                ob = opaque_s(ob);
+                os = opaque_s(os);
+            }
         });
     }
 }
