@@ -70,9 +70,15 @@ int zt_device_count(int* count);
 int zt_ctx_create(int device, zt_ctx** out);
 int zt_ctx_destroy(zt_ctx* ctx);
 /* Run subsequent work on an external stream (e.g. torch.cuda.current_stream().cuda_stream).
- * The handle is used verbatim: NULL is the device's default (null) stream. */
+ * The handle is used verbatim: NULL is the device's default (null) stream.
+ * After a switch to a different stream, everything the context issues is ordered after
+ * everything it issued before the switch (the new stream waits for an event recorded on the old
+ * one: the context's calls share one scratch buffer). A call that sets the stream it already has
+ * does nothing. A stream handed to the context is synchronised before it is destroyed: the
+ * context cannot order after a stream that no longer exists. */
 int zt_ctx_set_stream(zt_ctx* ctx, void* hip_stream);
-/* Return to the context's own (non-blocking) stream, the state after zt_ctx_create. */
+/* Return to the context's own (non-blocking) stream, the state after zt_ctx_create; a switch
+ * like zt_ctx_set_stream's, with the same ordering. */
 int zt_ctx_use_own_stream(zt_ctx* ctx);
 int zt_ctx_get_stream(zt_ctx* ctx, void** hip_stream);
 int zt_ctx_synchronize(zt_ctx* ctx);

@@ -65,6 +65,9 @@ struct zt_ctx {
     hipStream_t own = nullptr;
     hipStream_t cur = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipEvent_t ev_switch = nullptr;  // orders a new stream after the one it replaces
+    bool issued = false;    // an entry point has run since the last switch: `cur` may hold work
+    bool recorded = false;  // ev_switch has been recorded: earlier work may still be pending
     bool timed = false;
     void* scratch = nullptr;
     size_t scratch_bytes = 0;
@@ -104,6 +107,15 @@ struct DeviceGuard {
 
 int check_ctx(zt_ctx* ctx) {
     if (!ctx) return fail(ZT_ERR_INVALID_PARAMETERS, "null context");
+    return ZT_OK;
+}
+
+// The first step of every entry point that issues work on the context's stream (or hands the
+// stream out): check_ctx, and a note that the current stream may hold the context's work from now
+// on (switch_stream).
+int begin_call(zt_ctx* ctx) {
+    if (int rc = check_ctx(ctx)) return rc;
+    ctx->issued = true;
     return ZT_OK;
 }
 
@@ -371,7 +383,12 @@ int zt_ctx_create(int device, zt_ctx** out) {
     zt_ctx* c = new zt_ctx();
     c->device = device;
     if (hipStreamCreateWithFlags(&c->own, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess) {
+        hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_switch, hipEventDisableTiming) != hipSuccess) {
+        if (c->ev_switch) (void)hipEventDestroy(c->ev_switch);
+        if (c->ev1) (void)hipEventDestroy(c->ev1);
+        if (c->ev0) (void)hipEventDestroy(c->ev0);
+        if (c->own) (void)hipStreamDestroy(c->own);
         delete c;
         return fail(ZT_ERR_DEVICE, "stream/event creation failed");
     }
@@ -388,27 +405,58 @@ int zt_ctx_destroy(zt_ctx* ctx) {
     if (ctx->scratch) (void)hipFree(ctx->scratch);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
+    if (ctx->ev_switch) (void)hipEventDestroy(ctx->ev_switch);
     if (ctx->own) (void)hipStreamDestroy(ctx->own);
     delete ctx;
     return ZT_OK;
 }
 
-int zt_ctx_set_stream(zt_ctx* ctx, void* hip_stream) {
+namespace {
+
+// The context's one scratch buffer (and whatever else its calls share) is only safe while all of
+// its work is ordered. A switch to a different stream therefore makes the new stream wait for an
+// event recorded on the old one: everything issued from now on runs after everything issued so
+// far. Setting the stream the context already has costs nothing, so a caller that sets the same
+// stream before every call (default_context(), the device chains) issues no extra work. A stream
+// that no entry point has used is left without a new record (a new context given its stream: the
+// own stream then never receives a command), but the new stream still waits for the last record,
+// so the order also holds across switches with no call between them (A -> B -> C: C waits for A).
+int switch_stream(zt_ctx* ctx, hipStream_t s) {
     if (int rc = check_ctx(ctx)) return rc;
+    if (s == ctx->cur) return ZT_OK;
+    DeviceGuard g(ctx->device);
+    if (ctx->issued) {
+        const hipError_t e = hipEventRecord(ctx->ev_switch, ctx->cur);
+        if (e == hipSuccess) {
+            ctx->recorded = true;
+        } else if (e == hipErrorInvalidHandle || e == hipErrorContextIsDestroyed) {
+            // the caller has destroyed the stream being left, which it may only do once the work
+            // on it is done (zarrs_tools_amd.h): nothing new is left to wait for
+            (void)hipGetLastError();
+        } else {
+            return hip_fail(e, "hipEventRecord at a stream switch");
+        }
+    }
+    if (ctx->recorded) ZT_HIP(hipStreamWaitEvent(s, ctx->ev_switch, 0));
+    ctx->cur = s;
+    ctx->issued = false;
+    return ZT_OK;
+}
+
+}  // namespace
+
+int zt_ctx_set_stream(zt_ctx* ctx, void* hip_stream) {
     // Used verbatim: NULL is the device's default (null) stream, which is what
     // torch.cuda.current_stream().cuda_stream returns for torch's default stream.
-    ctx->cur = static_cast<hipStream_t>(hip_stream);
-    return ZT_OK;
+    return switch_stream(ctx, static_cast<hipStream_t>(hip_stream));
 }
 
 int zt_ctx_use_own_stream(zt_ctx* ctx) {
-    if (int rc = check_ctx(ctx)) return rc;
-    ctx->cur = ctx->own;
-    return ZT_OK;
+    return switch_stream(ctx, ctx ? ctx->own : nullptr);
 }
 
 int zt_ctx_get_stream(zt_ctx* ctx, void** hip_stream) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;  // the caller may issue work on the stream it gets
     if (!hip_stream) return fail(ZT_ERR_INVALID_PARAMETERS, "null output pointer");
     *hip_stream = ctx->cur;
     return ZT_OK;
@@ -492,7 +540,7 @@ int zt_guided_filter_apply_ndarray(zt_ctx* ctx, int dtype_in, const void* in,
                                    const int64_t* out_start, const int64_t* out_shape,
                                    int dtype_out, void* out, const int64_t* out_strides,
                                    float epsilon, int radius) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (int rc = dtypes_ok(dtype_in, dtype_out)) return rc;
     if (int rc = radius_ok(radius)) return rc;
     if (int rc = check_shape(in_shape, ndim, "in_shape")) return rc;
@@ -537,7 +585,7 @@ int zt_guided_filter_apply_array(zt_ctx* ctx, int dtype_in, const void* in, int 
                                  const int64_t* chunk_shape, float epsilon, int radius,
                                  const int64_t* chunk_grid_start,
                                  const int64_t* chunk_grid_count) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (int rc = dtypes_ok(dtype_in, dtype_out)) return rc;
     if (int rc = radius_ok(radius)) return rc;
     if (int rc = check_shape(shape, ndim, "shape")) return rc;
@@ -664,7 +712,7 @@ int zt_guided_filter_apply_slab(zt_ctx* ctx, int dtype_in, const void* in, int d
                                 void* out, const int64_t* global_shape, int64_t in_z0,
                                 int64_t in_nz, int64_t out_z0, int64_t out_nz,
                                 const int64_t* chunk_shape, float epsilon, int radius) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (int rc = dtypes_ok(dtype_in, dtype_out)) return rc;
     if (int rc = radius_ok(radius)) return rc;
     if (int rc = check_shape(global_shape, 3, "global_shape")) return rc;
@@ -888,7 +936,7 @@ int zt_gaussian_apply_ndarray(zt_ctx* ctx, int dtype_in, const void* in, const i
                               int ndim, const int64_t* out_start, const int64_t* out_shape,
                               int dtype_out, void* out, const float* sigma,
                               const int64_t* kernel_half_size) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (int rc = dtypes_ok(dtype_in, dtype_out)) return rc;
     if (int rc = check_shape(in_shape, ndim, "in_shape")) return rc;
     if (int rc = gaussian_args_ok(sigma, kernel_half_size, ndim)) return rc;
@@ -907,7 +955,7 @@ int zt_gaussian_apply_ndarray(zt_ctx* ctx, int dtype_in, const void* in, const i
 int zt_gaussian_apply_array(zt_ctx* ctx, int dtype_in, const void* in, int dtype_out, void* out,
                             const int64_t* shape, int ndim, const int64_t* chunk_shape,
                             const float* sigma, const int64_t* kernel_half_size) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (int rc = dtypes_ok(dtype_in, dtype_out)) return rc;
     if (int rc = check_shape(shape, ndim, "shape")) return rc;
     if (int rc = gaussian_args_ok(sigma, kernel_half_size, ndim)) return rc;
@@ -1038,7 +1086,7 @@ int zt_gradient_magnitude_apply_ndarray(zt_ctx* ctx, int dtype_in, const void* i
                                         const int64_t* in_shape, int ndim,
                                         const int64_t* out_start, const int64_t* out_shape,
                                         int dtype_out, void* out, int op) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (int rc = dtypes_ok(dtype_in, dtype_out)) return rc;
     if (int rc = check_shape(in_shape, ndim, "in_shape")) return rc;
     if (int rc = gm_op_ok(op)) return rc;
@@ -1057,7 +1105,7 @@ int zt_gradient_magnitude_apply_ndarray(zt_ctx* ctx, int dtype_in, const void* i
 int zt_gradient_magnitude_apply_array(zt_ctx* ctx, int dtype_in, const void* in, int dtype_out,
                                       void* out, const int64_t* shape, int ndim,
                                       const int64_t* chunk_shape, int op) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (int rc = dtypes_ok(dtype_in, dtype_out)) return rc;
     if (int rc = check_shape(shape, ndim, "shape")) return rc;
     if (int rc = gm_op_ok(op)) return rc;
@@ -1226,7 +1274,7 @@ int zt_rank_filter_apply_ndarray(zt_ctx* ctx, int dtype_in, const void* in,
                                  const int64_t* in_shape, int ndim, const int64_t* out_start,
                                  const int64_t* out_shape, int dtype_out, void* out, int kind,
                                  const int64_t* kernel_half_size) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (int rc = dtypes_ok(dtype_in, dtype_out)) return rc;
     if (int rc = check_shape(in_shape, ndim, "in_shape")) return rc;
     if (int rc = rank_args_ok(kind, kernel_half_size, ndim)) return rc;
@@ -1247,7 +1295,7 @@ int zt_rank_filter_apply_array(zt_ctx* ctx, int dtype_in, const void* in, int dt
                                void* out, const int64_t* shape, int ndim,
                                const int64_t* chunk_shape, int kind,
                                const int64_t* kernel_half_size) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (int rc = dtypes_ok(dtype_in, dtype_out)) return rc;
     if (int rc = check_shape(shape, ndim, "shape")) return rc;
     if (int rc = rank_args_ok(kind, kernel_half_size, ndim)) return rc;
@@ -1310,7 +1358,7 @@ int zt_summed_area_table_memory_per_chunk(int dtype_in, int dtype_out, const int
 int zt_summed_area_table_apply_ndarray(zt_ctx* ctx, int dtype_in, const void* in,
                                        const int64_t* shape, int ndim, int dtype_out, void* out,
                                        void* carry) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (int rc = dtypes_ok(dtype_in, dtype_out)) return rc;
     if (int rc = check_shape(shape, ndim, "shape")) return rc;
     if (numel(shape, ndim) == 0) return ZT_OK;
@@ -1323,7 +1371,7 @@ int zt_summed_area_table_apply_ndarray(zt_ctx* ctx, int dtype_in, const void* in
 int zt_summed_area_table_apply_array(zt_ctx* ctx, int dtype_in, const void* in, int dtype_out,
                                      void* out, const int64_t* shape, int ndim,
                                      const int64_t* chunk_shape) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (int rc = dtypes_ok(dtype_in, dtype_out)) return rc;
     if (int rc = check_shape(shape, ndim, "shape")) return rc;
     if (!chunk_shape) return fail(ZT_ERR_INVALID_PARAMETERS, "null chunk_shape");
@@ -1469,7 +1517,7 @@ int zt_pointwise_memory_per_chunk(int kind, int dtype_in, int dtype_out,
 int zt_pointwise_apply_ndarray(zt_ctx* ctx, int dtype_in, const void* in, const int64_t* in_shape,
                                int ndim, const int64_t* sub_start, const int64_t* sub_shape,
                                const zt_pointwise_op* ops, int n_ops, void* out) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (int rc = check_shape(in_shape, ndim, "in_shape")) return rc;
     zt::PwProgram prog;
     if (int rc = build_pointwise_program(dtype_in, ops, n_ops, &prog)) return rc;
@@ -1547,7 +1595,7 @@ int zt_arithmetic_memory_per_chunk(int op, int dtype_a, int dtype_b, int dtype_o
 
 int zt_arithmetic_apply(zt_ctx* ctx, int op, int dtype_a, const void* a, int dtype_b,
                         const void* b, int64_t n, int dtype_out, void* out) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (int rc = zt_arithmetic_is_compatible(op, dtype_a, dtype_b, dtype_out)) return rc;
     if (n < 0) return fail(ZT_ERR_INVALID_PARAMETERS, "negative element count");
     if (n == 0) return ZT_OK;
@@ -1615,7 +1663,7 @@ int zt_connected_components_memory(int dtype_in, int dtype_out, const int64_t* s
 int zt_connected_components_apply_array(zt_ctx* ctx, int dtype_in, const void* in, int dtype_out,
                                         void* out, const int64_t* shape, int ndim,
                                         int connectivity, uint64_t* count) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (int rc = zt_connected_components_is_compatible(dtype_in, dtype_out)) return rc;
     if (int rc = check_shape(shape, ndim, "shape")) return rc;
     if (connectivity < 1 || connectivity > ndim)
@@ -1722,7 +1770,7 @@ int zt_distance_transform_memory(int dtype_in, int dtype_out, const int64_t* sha
 int zt_distance_transform_apply_array(zt_ctx* ctx, int dtype_in, const void* in, int dtype_out,
                                       void* out, const int64_t* shape, const int64_t* spacing,
                                       int ndim, int squared) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (int rc = zt_distance_transform_is_compatible(dtype_in, dtype_out)) return rc;
     zt::EdtPlan plan;
     if (int rc = edt_check(shape, spacing, ndim, &plan)) return rc;
@@ -1821,7 +1869,7 @@ int zt_label_statistics_state_bytes(int ndim, int64_t n_labels, int with_intensi
 
 int zt_label_statistics_init(zt_ctx* ctx, int ndim, int64_t n_labels, int with_intensity,
                              void* state) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (int rc = lbl_ndim_ok(ndim)) return rc;
     zt::LblPlan plan;
     if (int rc = lbl_fail(zt::lbl_state(ndim, n_labels, with_intensity != 0, false, &plan),
@@ -1838,7 +1886,7 @@ int zt_label_statistics_accumulate(zt_ctx* ctx, int dtype_labels, const void* la
                                    int dtype_intensity, const void* intensity,
                                    const int64_t* box_shape, const int64_t* origin, int ndim,
                                    int64_t n_labels, void* state) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (int rc = zt_label_statistics_is_compatible(dtype_labels, dtype_intensity)) return rc;
     if (int rc = check_shape(box_shape, ndim, "box_shape")) return rc;
     if ((dtype_intensity == ZT_NO_DTYPE) != (intensity == nullptr))
@@ -1867,7 +1915,7 @@ int zt_label_statistics_accumulate(zt_ctx* ctx, int dtype_labels, const void* la
 
 int zt_label_statistics_finish(zt_ctx* ctx, const void* state, int ndim, int64_t n_labels,
                                int with_intensity, uint64_t* host_state, uint64_t* invalid) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (int rc = lbl_ndim_ok(ndim)) return rc;
     zt::LblPlan plan;
     if (int rc = lbl_fail(zt::lbl_state(ndim, n_labels, with_intensity != 0, false, &plan),
@@ -1940,7 +1988,7 @@ int zt_label_size_filter_memory(int dtype_in, int dtype_out, const int64_t* shap
 int zt_label_size_filter_apply_array(zt_ctx* ctx, int dtype_in, const void* in, int dtype_out,
                                      void* out, const int64_t* shape, int ndim, int64_t min_size,
                                      int64_t max_size, int relabel, uint64_t* kept) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (int rc = zt_label_size_filter_is_compatible(dtype_in, dtype_out)) return rc;
     if (int rc = lsf_sizes_ok(min_size, max_size)) return rc;
     int64_t n = 0;
@@ -2055,7 +2103,7 @@ int zt_reconstruction_memory(int dtype, int marker_mode, const int64_t* shape, i
 int zt_reconstruction_apply_array(zt_ctx* ctx, int dtype, const void* mask, const void* marker,
                                   int marker_mode, double h, void* out, const int64_t* shape,
                                   int ndim, int connectivity, int method, uint64_t* rounds) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (int rc = zt_reconstruction_is_compatible(dtype, dtype, marker_mode)) return rc;
     if (int rc = check_shape(shape, ndim, "shape")) return rc;
     if (connectivity < 1 || connectivity > ndim)
@@ -2221,7 +2269,7 @@ int zt_watershed_apply_array(zt_ctx* ctx, int dtype_relief, const void* relief, 
                              const void* seeds, void* out, const int64_t* shape, int ndim,
                              int connectivity, int descending, int foreground_only,
                              int64_t rounds[3]) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (int rc = zt_watershed_is_compatible(dtype_relief, dtype_seeds)) return rc;
     if (int rc = check_shape(shape, ndim, "shape")) return rc;
     zt::RecGeom geom;
@@ -2332,7 +2380,7 @@ int zt_range_is_compatible(int dtype) { return info_dtype_ok(dtype); }
 int zt_histogram_is_compatible(int dtype) { return info_dtype_ok(dtype); }
 
 int zt_range_init(zt_ctx* ctx, void* state) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (!state || ((uintptr_t)state % 8) != 0)
         return fail(ZT_ERR_INVALID_PARAMETERS, "the range state is 16 device bytes, 8-byte aligned");
     DeviceGuard guard(ctx->device);
@@ -2342,7 +2390,7 @@ int zt_range_init(zt_ctx* ctx, void* state) {
 }
 
 int zt_range_accumulate(zt_ctx* ctx, int dtype, const void* in, int64_t n, void* state) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (int rc = info_dtype_ok(dtype)) return rc;
     if (int rc = info_run_ok(dtype, in, n)) return rc;
     if (!state || ((uintptr_t)state % 8) != 0)
@@ -2358,7 +2406,7 @@ int zt_range_accumulate(zt_ctx* ctx, int dtype, const void* in, int64_t n, void*
 
 int zt_range_finish(zt_ctx* ctx, int dtype, const void* state, uint64_t* min_bits,
                     uint64_t* max_bits, int* none) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (int rc = info_dtype_ok(dtype)) return rc;
     if (!state || !min_bits || !max_bits || !none)
         return fail(ZT_ERR_INVALID_PARAMETERS, "null pointer");
@@ -2377,7 +2425,7 @@ int zt_range_finish(zt_ctx* ctx, int dtype, const void* state, uint64_t* min_bit
 
 int zt_histogram_accumulate(zt_ctx* ctx, int dtype, const void* in, int64_t n, int64_t n_bins,
                             double min, double max, uint64_t* hist) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (int rc = info_dtype_ok(dtype)) return rc;
     if (int rc = histogram_args_ok(n_bins, min, max)) return rc;
     if (int rc = info_run_ok(dtype, in, n)) return rc;
@@ -2414,7 +2462,7 @@ int compare_state_ok(const void* state) {
 }  // namespace
 
 int zt_compare_init(zt_ctx* ctx, void* state) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (int rc = compare_state_ok(state)) return rc;
     DeviceGuard guard(ctx->device);
     hipError_t e = zt::launch_compare_init(state, ctx->cur);
@@ -2424,7 +2472,7 @@ int zt_compare_init(zt_ctx* ctx, void* state) {
 
 int zt_compare_accumulate(zt_ctx* ctx, int dtype, const void* a, const void* b, int64_t n,
                           int64_t base, void* state) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (!valid_dtype(dtype))
         return fail(ZT_ERR_UNSUPPORTED_DATA_TYPE, "Unsupported data type code %d", dtype);
     if (int rc = info_run_ok(dtype, a, n)) return rc;
@@ -2442,7 +2490,7 @@ int zt_compare_accumulate(zt_ctx* ctx, int dtype, const void* a, const void* b, 
 }
 
 int zt_compare_finish(zt_ctx* ctx, const void* state, uint64_t* n_diff, int64_t* first) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (!state || !n_diff || !first) return fail(ZT_ERR_INVALID_PARAMETERS, "null pointer");
     DeviceGuard guard(ctx->device);
     uint64_t words[2] = {0, 0};
@@ -2463,7 +2511,7 @@ int zt_chunk_occupancy_is_compatible(int dtype) {
 
 int zt_chunk_occupancy(zt_ctx* ctx, int dtype, const void* data, const int64_t* shape, int ndim,
                        const int64_t* cell_shape, uint64_t fill_bits, uint8_t* occupied) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (int rc = zt_chunk_occupancy_is_compatible(dtype)) return rc;
     if (!shape || !cell_shape || ndim < 1 || ndim > ZT_MAX_DIMS)
         return fail(ZT_ERR_INVALID_PARAMETERS, "shape / cell_shape of 1 to %d axes", ZT_MAX_DIMS);
@@ -2529,7 +2577,7 @@ int zt_downsample_input_subset(const int64_t* in_shape, int ndim, const int64_t*
 int zt_downsample_apply_ndarray(zt_ctx* ctx, int dtype_in, const void* in,
                                 const int64_t* in_shape, int ndim, const int64_t* stride,
                                 int discrete, int dtype_out, void* out) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (int rc = zt_downsample_is_compatible(dtype_in, dtype_out, discrete)) return rc;
     if (int rc = check_shape(in_shape, ndim, "in_shape")) return rc;
     if (!stride) return fail(ZT_ERR_INVALID_PARAMETERS, "null stride");
@@ -2581,7 +2629,7 @@ int zt_pyramid_level_shapes(const int64_t* shape, int ndim, const int64_t* facto
 int zt_pyramid_downsample(zt_ctx* ctx, int dtype, const void* level0, const int64_t* shape,
                           int ndim, const int64_t* factor, int max_levels, int discrete,
                           void* const* level_ptrs, int* levels_written) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (!level_ptrs || !levels_written) return fail(ZT_ERR_INVALID_PARAMETERS, "null pointers");
     std::vector<int64_t> shapes((size_t)std::max(max_levels, 1) * ZT_MAX_DIMS);
     int n = 0;
@@ -2643,7 +2691,7 @@ int zt_pyramid_downsample(zt_ctx* ctx, int dtype, const void* level0, const int6
 
 int zt_synth_step_noise_f32(zt_ctx* ctx, float* out, const int64_t* shape, int ndim,
                             const int64_t* global_shape, int64_t z0, uint64_t seed) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (int rc = check_shape(shape, ndim, "shape")) return rc;
     const int64_t* gs = global_shape ? global_shape : shape;
     int64_t n = numel(shape, ndim);
@@ -2659,7 +2707,7 @@ int zt_synth_step_noise_f32(zt_ctx* ctx, float* out, const int64_t* shape, int n
 int zt_synth_u16(zt_ctx* ctx, uint16_t* out, const int64_t* shape, int ndim,
                  const int64_t* global_shape, int64_t z0, uint64_t seed) {
     (void)global_shape;
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (int rc = check_shape(shape, ndim, "shape")) return rc;
     int64_t n = numel(shape, ndim);
     if (n == 0) return ZT_OK;
@@ -2672,7 +2720,7 @@ int zt_synth_u16(zt_ctx* ctx, uint16_t* out, const int64_t* shape, int ndim,
 
 int zt_reencode_cast(zt_ctx* ctx, int dtype_in, const void* in, int dtype_out, void* out,
                      int64_t n) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (zt::dtype_size(dtype_in) == 0 || zt::dtype_size(dtype_out) == 0)
         return fail(ZT_ERR_UNSUPPORTED_DATA_TYPE, "unsupported data type");
     if (n < 0) return fail(ZT_ERR_INVALID_PARAMETERS, "negative element count");
@@ -2686,7 +2734,7 @@ int zt_reencode_cast(zt_ctx* ctx, int dtype_in, const void* in, int dtype_out, v
 
 int zt_synth_box(zt_ctx* ctx, int kind, void* out, const int64_t* start, const int64_t* shape,
                  const int64_t* global_shape, int ndim, uint64_t seed) {
-    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = begin_call(ctx)) return rc;
     if (int rc = check_shape(shape, ndim, "shape")) return rc;
     if (int rc = check_shape(global_shape, ndim, "global_shape")) return rc;
     if (!start) return fail(ZT_ERR_INVALID_PARAMETERS, "null start");

@@ -90,6 +90,9 @@ class Context:
         return self._h
 
     def set_stream(self, stream) -> None:
+        """Run subsequent work on `stream` (a torch stream or a raw HIP stream handle). After a
+        switch to a different stream, everything the context issues is ordered after everything it
+        issued before the switch. A call that sets the stream it already has does nothing."""
         ptr = getattr(stream, "cuda_stream", stream)
         check(lib().zt_ctx_set_stream(self._h, ctypes.c_void_p(ptr)))
 
