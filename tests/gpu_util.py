@@ -84,6 +84,69 @@ def rel_err(out: np.ndarray, ref: np.ndarray) -> float:
     return float(np.max(np.abs(out - ref) / np.maximum(1.0, np.abs(ref))))
 
 
-# Float tolerance (stated in DESIGN.md §5): |gpu - ref| <= 1e-5 * max(1, |ref|). The GPU sums
-# box windows in f32 (fixed tree order); the reference in f64 through summed-area tables.
+# Float tolerance (stated in DESIGN.md §4, "Tolerance"): |gpu - ref| <= 1e-5 * max(1, |ref|). The
+# GPU sums box windows in f32 (fixed tree order); the reference in f64 through summed-area tables.
+# The figure was stated and measured on data in [0, 300): there max(1, |ref|) is relative for all
+# but the smallest values. For data outside [1, ~500) the same bound is taken relative to the
+# data's scale (scaled_rel_err): on values in [0, 1) the plain form is an absolute 1e-5, which a
+# result wrong by a percent passes, and at 1e14 its floor of 1 is far below one f32 ulp.
 FLOAT_TOL = 1e-5
+
+
+def value_scale(v: np.ndarray) -> float:
+    """The power of two S that puts max |v| into [256, 512): the value range of the [0, 300)
+    data at which FLOAT_TOL was stated and measured. Non-finite elements are left out."""
+    a = np.abs(np.asarray(v, dtype=np.float64))
+    top = float(a[np.isfinite(a)].max())
+    assert top > 0
+    return 2.0 ** (int(np.floor(np.log2(top))) - 8)
+
+
+def scaled_rel_err(out: np.ndarray, ref: np.ndarray, S: float) -> float:
+    """rel_err of the values in units of S (value_scale of the input): a power of two, so the
+    division is exact in f64 for every f32 value, subnormal ones included."""
+    return rel_err(out.astype(np.float64) / S, ref.astype(np.float64) / S)
+
+
+def assert_cast_bracketed(out: np.ndarray, ref_f32: np.ndarray, dout: str, S: float) -> None:
+    """An integer or 16-bit float output against the f32 reference, at any magnitude. The casts
+    are monotone, so an f32 result within t = FLOAT_TOL * S * max(1, |ref| / S) of the reference
+    lands in cast(ref - t) <= out <= cast(ref + t), elementwise (the ends are cast from f64, where
+    ref +- t is formed; an f32 value casts alike from either). 16-bit floats compare as values
+    (-0.0 == 0.0; +-inf are ordered); a NaN must meet a NaN."""
+    assert out.shape == ref_f32.shape and out.dtype == np.dtype(O.NP_STORAGE[dout]), (out.dtype,
+                                                                                      dout)
+    ref = ref_f32.astype(np.float64)
+    t = FLOAT_TOL * S * np.maximum(1.0, np.abs(ref) / S)
+    lo, hi = O.cast_from_f64(ref - t, dout), O.cast_from_f64(ref + t, dout)
+    if dout in ("float16", "bfloat16"):
+        out, lo, hi = (float_values(a, dout) for a in (out, lo, hi))
+        nan = np.isnan(ref)
+        bad = np.where(nan, ~np.isnan(out), ~((lo <= out) & (out <= hi)))
+    else:
+        bad = ~((lo <= out) & (out <= hi))
+    if bad.any():
+        i = tuple(int(k) for k in np.argwhere(bad)[0])
+        raise AssertionError(f"{int(bad.sum())} of {out.size} elements outside the bracket, first "
+                             f"at {i}: got {out[i]!r}, want [{lo[i]!r}, {hi[i]!r}] for the f32 "
+                             f"reference {ref_f32[i]!r} ({dout})")
+
+
+def type_extremes(shape, din, seed):
+    """The full range of an integer type (32- and 64-bit values round once to f32, to nearest
+    even); for float64, magnitudes up to 1e30 with values that `as f32` turns into +inf, -inf
+    (far apart, so no NaN arises), zero (1e-50) and a subnormal (1e-40)."""
+    rng = np.random.default_rng(seed)
+    if din == "float64":
+        v = rng.standard_normal(shape) * 10.0 ** rng.integers(-30, 31, shape)
+        flat = v.reshape(-1)
+        flat[flat.size // 5] = 1e300
+        flat[3 * flat.size // 5] = -3.5e38
+        flat[7] = 1e-50
+        flat[11] = -1e-40
+        flat[13] = -0.0
+        return v
+    info = np.iinfo(din)
+    v = rng.integers(info.min, info.max, shape, dtype=din, endpoint=True)
+    v.reshape(-1)[:4] = [info.max, info.min, info.max - 1, info.max // 2 + 1]
+    return v

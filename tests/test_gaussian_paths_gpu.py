@@ -21,7 +21,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
-from tests.gpu_util import assert_same_bits_nan, from_dev, poisoned, to_dev
+from tests.gpu_util import assert_same_bits_nan, from_dev, poisoned, to_dev, type_extremes
 
 pytestmark = pytest.mark.gpu
 
@@ -115,26 +115,6 @@ def test_yx_generic_input_types(din):
     and chunk by chunk."""
     v, v32 = typed_noise((33, 70), din, 3)
     check(v32, v, din, (16, 32), [1.0, 1.2], [2, 2], chunks_too=True)
-
-
-def type_extremes(shape, din, seed):
-    """The full range of an integer type (32- and 64-bit values round once to f32, to nearest
-    even); for float64, magnitudes up to 1e30 with values that `as f32` turns into +inf, -inf
-    (far apart, so no NaN arises), zero (1e-50) and a subnormal (1e-40)."""
-    rng = np.random.default_rng(seed)
-    if din == "float64":
-        v = rng.standard_normal(shape) * 10.0 ** rng.integers(-30, 31, shape)
-        flat = v.reshape(-1)
-        flat[flat.size // 5] = 1e300
-        flat[3 * flat.size // 5] = -3.5e38
-        flat[7] = 1e-50
-        flat[11] = -1e-40
-        flat[13] = -0.0
-        return v
-    info = np.iinfo(din)
-    v = rng.integers(info.min, info.max, shape, dtype=din, endpoint=True)
-    v.reshape(-1)[:4] = [info.max, info.min, info.max - 1, info.max // 2 + 1]
-    return v
 
 
 @pytest.mark.parametrize("din", ["int32", "uint32", "int64", "uint64", "float64"])

@@ -113,10 +113,17 @@ __device__ __forceinline__ float div_by_count(float x, float d, float rcp) {
     const float r = __builtin_fmaf(-q, d, x);
     return __builtin_fmaf(r, rcp, q);
 }
+// True where v_rcp_f32's result cannot be used: it flushes subnormals, so the reciprocal of a
+// d above 2^126 comes back as 0 and that of a subnormal d as inf (as gf_fused.hpp's).
+__device__ __forceinline__ bool rcp_unusable(float y) {
+    return __builtin_amdgcn_class(y, 0x2F4);  // -inf, -sub, -0, +0, +sub, +inf
+}
 // s / (s + eps): rcp, one Newton step and Markstein's correction (within 1 ulp, almost always
-// correctly rounded; 0/0 gives NaN as in the reference), as gf_fused.hpp's fast_div.
+// correctly rounded; 0/0 gives NaN as in the reference), as gf_fused.hpp's fast_div; a d outside
+// [2^-126, 2^126] takes the IEEE division.
 __device__ __forceinline__ float fast_div(float x, float d) {
     float y = __builtin_amdgcn_rcpf(d);
+    if (__builtin_expect(rcp_unusable(y), 0)) return x / d;
     const float e = __builtin_fmaf(-d, y, 1.0f);
     y = __builtin_fmaf(e, y, y);
     const float q = x * y;
@@ -427,11 +434,17 @@ __global__ __launch_bounds__(G4FConfig<R>::NT) void g4_fused_kernel(G4FParams p)
                     const f2 sq = d * d;  // (v - u).powf(2.0)
                     const f2 den = sq + (f2){p.eps, p.eps};
                     f2 y = {__builtin_amdgcn_rcpf(den.x), __builtin_amdgcn_rcpf(den.y)};
+                    const bool wx = rcp_unusable(y.x), wy = rcp_unusable(y.y);
                     const f2 e = pk_fma(-den, y, (f2){1.0f, 1.0f});
                     y = pk_fma(e, y, y);
                     q = sq * y;
                     r = pk_fma(-den, q, sq);
-                    const f2 a = pk_fma(r, y, q);
+                    f2 a = pk_fma(r, y, q);
+                    // s + eps outside [2^-126, 2^126]: IEEE division, in a rarely taken branch
+                    if (__builtin_expect((int)wx | (int)wy, 0)) {
+                        if (wx) a.x = sq.x / den.x;
+                        if (wy) a.y = sq.y / den.y;
+                    }
                     const f2 b = ((f2){1.0f, 1.0f} - a) * u;
                     const bool ok0 = c0 > 0 && t < T, ok1 = c1 > 0 && t < T;
                     float2* dst = Lab + (t * E1Y + ey0) * E1X + ex3;

@@ -327,11 +327,21 @@ template <typename T> struct S1 {
 template <> struct S1<uint8_t> { using acc = int; using in = int; static constexpr int HXB = 4; };
 template <> struct S1<uint16_t> { using acc = int; using in = int; static constexpr int HXB = 4; };
 
+// v_rcp_f32 flushes subnormals on both sides: the reciprocal of a d above 2^126 comes back as 0
+// (fast_div would return 0 where the quotient is near 1), that of a subnormal d as inf (NaN
+// after the correction). True for such a result (zero, subnormal or infinite), so one
+// v_cmp_class_f32 on the reciprocal tells whether d is inside [2^-126, 2^126].
+__device__ __forceinline__ bool rcp_unusable(float y) {
+    return __builtin_amdgcn_class(y, 0x2F4);  // -inf, -sub, -0, +0, +sub, +inf
+}
+
 // s / (s + eps): rcp + one Newton step + Markstein correction (6 VALU ops instead of the ~12 of
 // IEEE division; within 1 ulp, almost always correctly rounded). Special values follow IEEE:
-// 0/0 and inf/inf give NaN as in the reference.
+// 0/0 and inf/inf give NaN as in the reference. A d outside [2^-126, 2^126] (rcp_unusable)
+// takes the IEEE division, in a branch that tame data never enters.
 __device__ __forceinline__ float fast_div(float x, float d) {
     float y = __builtin_amdgcn_rcpf(d);
+    if (__builtin_expect(rcp_unusable(y), 0)) return x / d;
     float e = __builtin_fmaf(-d, y, 1.0f);
     y = __builtin_fmaf(e, y, y);
     float q = x * y;
@@ -973,6 +983,18 @@ __global__ __launch_bounds__(NT) void gf3d_fused_kernel(GFParams p) {
         for (int k = 0; k < NP3; ++k) r[k] = pk_fma(-den[k], q[k], sq[k]);
 #pragma unroll
         for (int k = 0; k < NP3; ++k) a[k] = pk_fma(r[k], y[k], q[k]);
+        // s + eps outside [2^-126, 2^126] (|v - u| >= 2^63, or subnormal): IEEE division for
+        // those elements, in a branch that data inside the range never enters
+        int wide = 0;
+#pragma unroll
+        for (int k = 0; k < NP3; ++k) wide |= (int)rcp_unusable(y[k].x) | (int)rcp_unusable(y[k].y);
+        if (__builtin_expect(wide != 0, 0)) {
+#pragma unroll
+            for (int k = 0; k < NP3; ++k) {
+                if (rcp_unusable(y[k].x)) a[k].x = sq[k].x / den[k].x;
+                if (rcp_unusable(y[k].y)) a[k].y = sq[k].y / den[k].y;
+            }
+        }
 #pragma unroll
         for (int k = 0; k < NP3; ++k) e[k] = (f2){1.0f, 1.0f} - a[k];
 #pragma unroll

@@ -376,9 +376,13 @@ __device__ __forceinline__ float g4_div_by_count(float x, float d, float rcp) {
     return __builtin_fmaf(r, rcp, q);
 }
 // s / (s + eps): rcp, one Newton step and Markstein's correction (within 1 ulp, almost always
-// correctly rounded; 0/0 gives NaN as in the reference), as gf_fused.hpp's fast_div.
+// correctly rounded; 0/0 gives NaN as in the reference), as gf_fused.hpp's fast_div. v_rcp_f32
+// flushes subnormals: the reciprocal of a d above 2^126 comes back as 0, that of a subnormal d
+// as inf; such a result (one v_cmp_class_f32) sends the element to the IEEE division.
 __device__ __forceinline__ float g4_fast_div(float x, float d) {
     float y = __builtin_amdgcn_rcpf(d);
+    if (__builtin_expect(__builtin_amdgcn_class(y, 0x2F4), 0))  // -inf, -sub, -0, +0, +sub, +inf
+        return x / d;
     const float e = __builtin_fmaf(-d, y, 1.0f);
     y = __builtin_fmaf(e, y, y);
     const float q = x * y;

@@ -22,8 +22,9 @@
 // Window sums along x and y use a fixed binary tree per output (pairs, quads, octets, ... plus
 // the remainder of 2r+1), so each sum's rounding depends only on its 2r+1 inputs, never on the
 // position inside the tile. The z-window of a and b is summed from the ring in the same tree
-// order. Only the v z-window is a running (add entering / subtract leaving) f32 sum, restarted
-// for every chunk-depth march.
+// order. Only the v z-window is a running (add entering / subtract leaving) sum, in f64 (int32
+// for 8- and 16-bit integer inputs: both exact), restarted for every chunk-depth march. A NaN or
+// an infinity that enters it never leaves it: see DESIGN.md §4 for what such input gives.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
