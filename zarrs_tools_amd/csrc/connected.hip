@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "zt_device.hpp"
+#include "zt_gpu.hpp"
 #include "zt_kernels.hpp"
 
 namespace zt {
@@ -48,11 +49,6 @@ static_assert(TX == 64, "a wave holds one x-row of a tile");
 static_assert(kRows % kWaves == 0 && TY > 1 && TZ > 1, "tile shape");
 static_assert(kCcBlockElems % kThreads == 0, "numbering block");
 
-template <int ESZ> struct UIntOf;
-template <> struct UIntOf<1> { using type = uint8_t; };
-template <> struct UIntOf<2> { using type = uint16_t; };
-template <> struct UIntOf<4> { using type = uint32_t; };
-template <> struct UIntOf<8> { using type = uint64_t; };
 
 __device__ inline uint32_t amin(uint32_t* p, uint32_t v) { return atomicMin(p, v); }
 __device__ inline uint64_t amin(uint64_t* p, uint64_t v) {

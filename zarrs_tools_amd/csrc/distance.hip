@@ -36,6 +36,7 @@
 #include <type_traits>
 
 #include "zt_device.hpp"
+#include "zt_gpu.hpp"
 #include "zt_edt_host.hpp"
 #include "zt_kernels.hpp"
 
@@ -49,11 +50,6 @@ constexpr int kWaves = kThreads / 64;
 // over the rest (a test reaches the loops with a few million rows, lines and output groups).
 constexpr unsigned kMaxBlocks = 1u << 14;
 
-template <int ESZ> struct UIntOf;
-template <> struct UIntOf<1> { using type = uint8_t; };
-template <> struct UIntOf<2> { using type = uint16_t; };
-template <> struct UIntOf<4> { using type = uint32_t; };
-template <> struct UIntOf<8> { using type = uint64_t; };
 
 // ---- innermost axis ----------------------------------------------------------------------------
 

@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include "zt_device.hpp"
+#include "zt_gpu.hpp"
 #include "zt_kernels.hpp"
 
 namespace zt {
@@ -82,68 +83,6 @@ struct G4FParams {
     int zseg, tiles_x, tiles_y;
     float eps;
 };
-
-__device__ __forceinline__ int fcount(int i, int n, int r) {
-    const int lo = i - r < 0 ? 0 : i - r;
-    const int hi = i + r > n - 1 ? n - 1 : i + r;
-    return hi - lo + 1;
-}
-
-// Buffer (SRD) loads: 32-bit byte offsets and the hardware range check (an offset past
-// num_records reads 0), so out-of-block points need no branch and no 64-bit address math.
-using rsrc_t = __amdgpu_buffer_rsrc_t;
-constexpr int kBad = (int)0x80000000;  // >= num_records of any slice: reads 0
-__device__ __forceinline__ rsrc_t make_rsrc(const void* base, uint32_t bytes) {
-    // built from kernel arguments and loop counters only (wave-uniform): stays in SGPRs
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)bytes,
-                                             0x00020000);
-}
-__device__ __forceinline__ float ldb(rsrc_t r, int off) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0));
-}
-
-// Packed pair of f32 (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32: both lanes in one issue).
-typedef float f2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f2 pk_fma(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
-
-// x / d for an integer count d given rcp = RN(1/d): Markstein's correction makes the quotient
-// correctly rounded (= IEEE division) in 3 VALU ops (as gf_fused.hpp's div_by_count).
-__device__ __forceinline__ float div_by_count(float x, float d, float rcp) {
-    const float q = x * rcp;
-    const float r = __builtin_fmaf(-q, d, x);
-    return __builtin_fmaf(r, rcp, q);
-}
-// True where v_rcp_f32's result cannot be used: it flushes subnormals, so the reciprocal of a
-// d above 2^126 comes back as 0 and that of a subnormal d as inf (as gf_fused.hpp's).
-__device__ __forceinline__ bool rcp_unusable(float y) {
-    return __builtin_amdgcn_class(y, 0x2F4);  // -inf, -sub, -0, +0, +sub, +inf
-}
-// s / (s + eps): rcp, one Newton step and Markstein's correction (within 1 ulp, almost always
-// correctly rounded; 0/0 gives NaN as in the reference), as gf_fused.hpp's fast_div; a d outside
-// [2^-126, 2^126] takes the IEEE division.
-__device__ __forceinline__ float fast_div(float x, float d) {
-    float y = __builtin_amdgcn_rcpf(d);
-    if (__builtin_expect(rcp_unusable(y), 0)) return x / d;
-    const float e = __builtin_fmaf(-d, y, 1.0f);
-    y = __builtin_fmaf(e, y, y);
-    const float q = x * y;
-    const float r = __builtin_fmaf(-d, q, x);
-    return __builtin_fmaf(r, y, q);
-}
-
-// Workgroup barrier for the LDS hand-offs only: __syncthreads() also fences global memory, which
-// would drain the loads kept in flight across it (the next slices' prefetches).
-__device__ __forceinline__ void lds_barrier() {
-    __asm__ volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-template <int B, int E, typename F>
-__device__ __forceinline__ void sfor(F&& f) {
-    if constexpr (B < E) {
-        f(std::integral_constant<int, B>{});
-        sfor<B + 1, E>(f);
-    }
-}
 
 // Q4: S1 reads 16-byte quads (4 consecutive x) instead of single elements: 4x fewer
 // vector-memory instructions for the stage-1 slices. Needs quads that never straddle the block
@@ -208,13 +147,13 @@ __global__ __launch_bounds__(G4FConfig<R>::NT) void g4_fused_kernel(G4FParams p)
     const int ot0 = p.o0[0], ot1 = p.o0[0] + p.on[0];
 
     // ---- S1 points: (ey, ex) of the stage-1 apron, the same for every timepoint ----------
-    int off[NPT];  // byte offset in the plane, or kBad outside the block / past the apron
+    int off[NPT];  // byte offset in the plane, or kBadOff outside the block / past the apron
 #pragma unroll
     for (int k = 0; k < NPT; ++k) {
         const int e = tid + k * NT;
         const int ey = e / E2X, ex = e - (e / E2X) * E2X;
         const int gy = y0 - 2 * R + ey, gx = x0 - 2 * R + ex;
-        off[k] = (e < C::NE2 && gy >= 0 && gy < ny && gx >= 0 && gx < nx) ? (gy * nx + gx) * 4 : kBad;
+        off[k] = (e < C::NE2 && gy >= 0 && gy < ny && gx >= 0 && gx < nx) ? (gy * nx + gx) * 4 : kBadOff;
     }
     const uint32_t plane_bytes = (uint32_t)(plane * 4);
     const char* vbytes = reinterpret_cast<const char*>(p.v);
@@ -225,7 +164,7 @@ __global__ __launch_bounds__(G4FConfig<R>::NT) void g4_fused_kernel(G4FParams p)
         const bool in = t < T && (unsigned)z < (unsigned)nz;  // wave-uniform
         return make_rsrc(vbytes + (in ? t * vol_bytes + z * plane_bytes64 : 0), in ? plane_bytes : 0u);
     };
-    auto ldv = [&](int t, int z, int o) -> float { return ldb(slice(t, z), o); };
+    auto ldv = [&](int t, int z, int o) -> float { return load_f32(slice(t, z), o); };
     const int zc_begin = zo_begin - R, zc_end = zo_end + R;  // stage-1 slices of this march
     // element form: every thread NPT apron points of every timepoint
     constexpr int TSE = Q4 ? 1 : TS, NPE = Q4 ? 1 : NPT;
@@ -250,7 +189,7 @@ __global__ __launch_bounds__(G4FConfig<R>::NT) void g4_fused_kernel(G4FParams p)
         for (int k = 0; k < NPQ; ++k) {
             const int qi = lq + LPT * k, ey = qi / NQR, cq = qi - (qi / NQR) * NQR;
             const int gy = y0 - 2 * R + ey, gx = x0 - 2 * R + 4 * cq;
-            offq[k] = (qi < NQT && gy >= 0 && gy < ny && gx >= 0 && gx < nx) ? (gy * nx + gx) * 4 : kBad;
+            offq[k] = (qi < NQT && gy >= 0 && gy < ny && gx >= 0 && gx < nx) ? (gy * nx + gx) * 4 : kBadOff;
             z1q[k] = qi < NQT ? (tq * E2Y + ey) * PZ + 4 * cq : -1;
 #pragma unroll
             for (int e = 0; e < 4; ++e) zq[k][e] = 0.0;
@@ -284,15 +223,15 @@ __global__ __launch_bounds__(G4FConfig<R>::NT) void g4_fused_kernel(G4FParams p)
 #pragma unroll
     for (int j = 0; j < C::KY3; ++j) {
         const int ey = sg3 * C::KY3 + j, gy = y0 - R + ey;
-        off3[j] = (i3 >= 0 && ey < E1Y && gy >= 0 && gy < ny && gx3 >= 0 && gx3 < nx) ? (gy * nx + gx3) * 4 : kBad;
+        off3[j] = (i3 >= 0 && ey < E1Y && gy >= 0 && gy < ny && gx3 >= 0 && gx3 < nx) ? (gy * nx + gx3) * 4 : kBadOff;
     }
     float v3[TS][C::KY3];  // v at the S3 points of the current stage-1 slice (prefetched)
     // ---- S5 item: output (y, x) of the tile ----------------------------------------------
     const int x5 = tid % TX, y5 = tid / TX;  // tid < TX * TY
     const int gx5 = x0 + x5, gy5 = y0 + y5;
     const bool live5 = tid < C::NI5 && gx5 < xe && gy5 < ye;
-    const int off5 = live5 ? (gy5 * nx + gx5) * 4 : kBad;
-    const int cyx5 = live5 ? fcount(gy5, ny, R) * fcount(gx5, nx, R) : 0;
+    const int off5 = live5 ? (gy5 * nx + gx5) * 4 : kBadOff;
+    const int cyx5 = live5 ? clamped_count(gy5, ny, R) * clamped_count(gx5, nx, R) : 0;
     float v5[TS];
     // stage-2 z-window: the sum of the last W slice sums P, kept in LDS (each thread only touches
     // its own slots, so no barrier), summed in a fixed slot order without subtraction
@@ -303,7 +242,7 @@ __global__ __launch_bounds__(G4FConfig<R>::NT) void g4_fused_kernel(G4FParams p)
         for (int t = 0; t < TS; ++t) {
             const rsrc_t rs = slice(t, zc);
 #pragma unroll
-            for (int j = 0; j < C::KY3; ++j) v3[t][j] = ldb(rs, off3[j]);
+            for (int j = 0; j < C::KY3; ++j) v3[t][j] = load_f32(rs, off3[j]);
         }
     };
     auto load_v5 = [&](int zo) {
@@ -361,8 +300,8 @@ __global__ __launch_bounds__(G4FConfig<R>::NT) void g4_fused_kernel(G4FParams p)
                 const rsrc_t ra = slice(t, zc + 1 + R), rl = slice(t, zc - R);
 #pragma unroll
                 for (int k = 0; k < NPT; ++k) {
-                    pa[t][k] = ldb(ra, off[k]);
-                    ps[t][k] = ldb(rl, off[k]);
+                    pa[t][k] = load_f32(ra, off[k]);
+                    ps[t][k] = load_f32(rl, off[k]);
                 }
             }
             }
@@ -407,11 +346,11 @@ __global__ __launch_bounds__(G4FConfig<R>::NT) void g4_fused_kernel(G4FParams p)
                     }
                 }
                 const bool zin = (unsigned)zc < (unsigned)nz;
-                const int czx = zin && gx3 >= 0 && gx3 < nx ? fcount(zc, nz, R) * fcount(gx3, nx, R) : 0;
+                const int czx = zin && gx3 >= 0 && gx3 < nx ? clamped_count(zc, nz, R) * clamped_count(gx3, nx, R) : 0;
                 static_assert(C::KY3 == 2, "the pointwise stage works on the item's row pair");
                 const int ey0 = sg3 * 2, gyp = y0 - R + ey0;
-                const int cz0 = gyp >= 0 && gyp < ny ? czx * fcount(gyp, ny, R) : 0;
-                const int cz1 = gyp + 1 >= 0 && gyp + 1 < ny ? czx * fcount(gyp + 1, ny, R) : 0;
+                const int cz0 = gyp >= 0 && gyp < ny ? czx * clamped_count(gyp, ny, R) : 0;
+                const int cz1 = gyp + 1 >= 0 && gyp + 1 < ny ? czx * clamped_count(gyp + 1, ny, R) : 0;
 #pragma unroll
                 for (int t = 0; t < TS; ++t) {
                     double U0 = 0.0, U1 = 0.0;
@@ -494,7 +433,7 @@ __global__ __launch_bounds__(G4FConfig<R>::NT) void g4_fused_kernel(G4FParams p)
                     ring[(slot * TS + t) * (TY * TX) + tid] = sab;
                 }
                 if (i >= 2 * R && live5) {
-                    const int cz5 = fcount(zo, nz, R) * cyx5;
+                    const int cz5 = clamped_count(zo, nz, R) * cyx5;
 #pragma unroll
                     for (int t = 0; t < TS; ++t) {
                         if (t < ot0 || t >= ot1) continue;

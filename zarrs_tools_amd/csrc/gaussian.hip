@@ -19,6 +19,7 @@
 #include <type_traits>
 
 #include "zt_device.hpp"
+#include "zt_gpu.hpp"
 #include "zt_kernels.hpp"
 
 namespace zt {
@@ -326,27 +327,10 @@ hipError_t launch_gaussian_yx(const void* in, int dtype_in, float* out, int64_t 
 // ---------------------------------------------------------------------------------------------
 constexpr int kZYXTy = 32, kZYXTx = 64, kZYXSegMin = 32;
 
-template <int B, int E, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (B < E) {
-        f(std::integral_constant<int, B>{});
-        static_for<B + 1, E>(f);
-    }
-}
-
-// Buffer (SRD) access for the march: the slice base goes in a wave-uniform descriptor, each
-// point keeps a 32-bit byte offset, and an offset past num_records reads 0 / drops the store,
-// so the march has no branches around its memory instructions: hipcc's vmcnt accounting then
-// waits for exactly the step-old prefetch, instead of draining every load (a guarded prefetch
-// and __syncthreads() each forced vmcnt(0) per step).
-using zrsrc_t = __amdgpu_buffer_rsrc_t;
-constexpr int kZBad = (int)0x80000000;
-__device__ __forceinline__ zrsrc_t z_rsrc(const void* base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)bytes,
-                                             0x00020000);
-}
+// One element through a slice descriptor (zt_gpu.hpp): the march has no branch around its memory
+// instructions (a guarded prefetch and __syncthreads() each forced vmcnt(0) per step).
 template <typename T>
-__device__ __forceinline__ float z_load(zrsrc_t r, int off) {
+__device__ __forceinline__ float z_load(rsrc_t r, int off) {
     if constexpr (sizeof(T) == 1) {
         const uint8_t b = __builtin_amdgcn_raw_buffer_load_b8(r, off, 0, 0);
         return Elem<T>::to_f32(__builtin_bit_cast(T, b));
@@ -362,35 +346,18 @@ __device__ __forceinline__ float z_load(zrsrc_t r, int off) {
         return Elem<T>::to_f32(__builtin_bit_cast(T, b));
     }
 }
-// LDS hand-off barrier that leaves the global prefetches in flight (see gf_fused.hpp)
-__device__ __forceinline__ void z_lds_barrier() {
-    __asm__ volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
 
 // 4 consecutive elements from one buffer access (16/8/4 bytes for 4/2/1-byte types)
 template <typename T>
-__device__ __forceinline__ void z_load4(zrsrc_t r, int off, float (&v)[4]) {
-    if constexpr (sizeof(T) == 4) {
-        typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-        const u4 q = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
-        // elements copied out first: clang's bit_cast of a vector element lvalue reads element 0
-        const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+__device__ __forceinline__ void z_load4(rsrc_t r, int off, float (&v)[4]) {
+    typedef unsigned int u4 __attribute__((ext_vector_type(4)));
+    typedef unsigned int u2 __attribute__((ext_vector_type(2)));
+    typename UIntOf<sizeof(T)>::type w[4];
+    if constexpr (sizeof(T) == 4) unpack4((u4)__builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0), w);
+    else if constexpr (sizeof(T) == 2) unpack4((u2)__builtin_amdgcn_raw_buffer_load_b64(r, off, 0, 0), w);
+    else unpack4((uint32_t)__builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0), w);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = Elem<T>::to_f32(__builtin_bit_cast(T, w[e]));
-    } else if constexpr (sizeof(T) == 2) {
-        typedef unsigned int u2 __attribute__((ext_vector_type(2)));
-        const u2 q = __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, 0);
-        v[0] = Elem<T>::to_f32(__builtin_bit_cast(T, (uint16_t)(q.x & 0xffffu)));
-        v[1] = Elem<T>::to_f32(__builtin_bit_cast(T, (uint16_t)(q.x >> 16)));
-        v[2] = Elem<T>::to_f32(__builtin_bit_cast(T, (uint16_t)(q.y & 0xffffu)));
-        v[3] = Elem<T>::to_f32(__builtin_bit_cast(T, (uint16_t)(q.y >> 16)));
-    } else {
-        static_assert(sizeof(T) == 1, "quad loads of 1/2/4-byte elements");
-        const uint32_t q = __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0);
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            v[e] = Elem<T>::to_f32(__builtin_bit_cast(T, (uint8_t)((q >> (8 * e)) & 0xffu)));
-    }
+    for (int e = 0; e < 4; ++e) v[e] = Elem<T>::to_f32(__builtin_bit_cast(T, w[e]));
 }
 
 // A workgroup stages the (TY + L - 1) x (TX + 2 MG) input tile from x0 - MG, MG = L/2 rounded up
@@ -457,13 +424,13 @@ __global__ __launch_bounds__(CFG::NT) __attribute__((amdgpu_waves_per_eu(CFG::NT
                 bl |= xs < 0 ? 1 << k : 0;
                 br |= xs > nx - 4 ? 1 << k : 0;
                 xs = xs < 0 ? 0 : (xs > nx - 4 ? nx - 4 : xs);
-                off[k] = q < NQ ? (int)((qy * nx + xs) * (int64_t)sizeof(TIn)) : kZBad;
+                off[k] = q < NQ ? (int)((qy * nx + xs) * (int64_t)sizeof(TIn)) : kBadOff;
             } else {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     int64_t qx = qx4 + 4 * cq + e;
                     qx = qx < 0 ? 0 : (qx > nx - 1 ? nx - 1 : qx);
-                    off[4 * k + e] = q < NQ ? (int)((qy * nx + qx) * (int64_t)sizeof(TIn)) : kZBad;
+                    off[4 * k + e] = q < NQ ? (int)((qy * nx + qx) * (int64_t)sizeof(TIn)) : kBadOff;
                 }
             }
         }
@@ -472,7 +439,7 @@ __global__ __launch_bounds__(CFG::NT) __attribute__((amdgpu_waves_per_eu(CFG::NT
                 reinterpret_cast<const char*>(in) + o * nz * plane * (int64_t)sizeof(TIn);
             auto ld = [&](int64_t zq, float (&v)[NPQ][4]) {  // input slice zq (clamped)
                 zq = zq < 0 ? 0 : (zq > nz - 1 ? nz - 1 : zq);
-                const zrsrc_t rs = z_rsrc(vol + zq * plane * (int64_t)sizeof(TIn), plane_bytes);
+                const rsrc_t rs = make_rsrc(vol + zq * plane * (int64_t)sizeof(TIn), plane_bytes);
 #pragma unroll
                 for (int k = 0; k < NPQ; ++k) {
                     if constexpr (QUAD) {
@@ -536,7 +503,7 @@ __global__ __launch_bounds__(CFG::NT) __attribute__((amdgpu_waves_per_eu(CFG::NT
                         *reinterpret_cast<float4*>(tile + 4 * (tid + NT * k)) =
                             make_float4(sv[0], sv[1], sv[2], sv[3]);
                     }
-                    z_lds_barrier();
+                    lds_barrier();
 #pragma unroll
                     for (int ip = 0; ip < NYP; ++ip) {  // y pass, 4 rows per item
                         const int item = tid + NT * ip;
@@ -556,8 +523,8 @@ __global__ __launch_bounds__(CFG::NT) __attribute__((amdgpu_waves_per_eu(CFG::NT
                             }
                         }
                     }
-                    z_lds_barrier();
-                    const zrsrc_t ro = z_rsrc(obase + (kz < kz1 ? kz : 0) * ony * onx * 4,
+                    lds_barrier();
+                    const rsrc_t ro = make_rsrc(obase + (kz < kz1 ? kz : 0) * ony * onx * 4,
                                               kz < kz1 ? oplane_bytes : 0u);
 #pragma unroll
                     for (int ip = 0; ip < NXP; ++ip) {  // x pass, 4 columns per item
@@ -582,19 +549,19 @@ __global__ __launch_bounds__(CFG::NT) __attribute__((amdgpu_waves_per_eu(CFG::NT
                             const u4 q = {__float_as_uint(o4[0]), __float_as_uint(o4[1]),
                                           __float_as_uint(o4[2]), __float_as_uint(o4[3])};
                             __builtin_amdgcn_raw_buffer_store_b128(
-                                q, ro, live && c0 < hx ? ooff : kZBad, 0, 2);
+                                q, ro, live && c0 < hx ? ooff : kBadOff, 0, 2);
                         } else {
 #pragma unroll
                             for (int k = 0; k < 4; ++k)
                                 __builtin_amdgcn_raw_buffer_store_b32(
                                     __float_as_uint(o4[k]), ro,
-                                    live && c0 + k < hx ? ooff + 4 * k : kZBad, 0, 2);
+                                    live && c0 + k < hx ? ooff + 4 * k : kBadOff, 0, 2);
                         }
                     }
                     // the next tile / ybuf writes follow this step's barriers
                 });
             }
-            z_lds_barrier();  // the last step's reads of tile / ybuf before the next volume
+            lds_barrier();  // the last step's reads of tile / ybuf before the next volume
         }
     }
 }
@@ -626,7 +593,7 @@ struct ZYXWide { static constexpr int TY = 32, TX = 256, NT = 1024; };
 //   own DMA of slice k + 1 + MID landed (vmcnt) ; barrier 2 ; pre <- that slot ; x pass, stores.
 // Same arithmetic, in the same order, as gauss_zyx_kernel: bit-identical output.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void zdma16(zrsrc_t r, int voff, unsigned lds) {
+__device__ __forceinline__ void zdma16(rsrc_t r, int voff, unsigned lds) {
     unsigned keep;
     asm volatile(
         "s_mov_b32 %0, m0\n\t"
@@ -692,7 +659,7 @@ __global__ __launch_bounds__(1024) void gauss_zyx_dma_kernel(const float* __rest
         bl |= xs < 0 ? 1 << k : 0;
         br |= xs > nx - 4 ? 1 << k : 0;
         xs = xs < 0 ? 0 : (xs > nx - 4 ? nx - 4 : xs);
-        off[k] = q < NQ ? (int)((qy * nx + xs) * 4) : kZBad;
+        off[k] = q < NQ ? (int)((qy * nx + xs) * 4) : kBadOff;
     }
     auto fix = [&](float (&v)[NPQ][4]) {
         if (edgex) {
@@ -708,12 +675,12 @@ __global__ __launch_bounds__(1024) void gauss_zyx_dma_kernel(const float* __rest
         const char* vol = reinterpret_cast<const char*>(in) + o * nz * plane * 4;
         auto rs_of = [&](int64_t zq) {
             zq = zq < 0 ? 0 : (zq > nz - 1 ? nz - 1 : zq);
-            return z_rsrc(vol + zq * plane * 4, plane_bytes);
+            return make_rsrc(vol + zq * plane * 4, plane_bytes);
         };
         // this wave's pieces of slice zq into slot sl: piece j = wave + 16 k carries quads
         // [64 j, 64 j + 64), i.e. lane l's own quad tid + NT k
         auto dma = [&](int64_t zq, int sl) {
-            const zrsrc_t rs = rs_of(zq);
+            const rsrc_t rs = rs_of(zq);
             const unsigned base = slot_base + (unsigned)sl * (NJ * 1024u);
             zdma16(rs, off[0], base + (unsigned)wave * 1024u);
             zdma16(rs, off[1], base + (unsigned)(wave + 16) * 1024u);
@@ -732,7 +699,7 @@ __global__ __launch_bounds__(1024) void gauss_zyx_dma_kernel(const float* __rest
         // window of the first output slice: slices o0 + kz0 + i - MID, i < L - 1, by plain loads
 #pragma unroll
         for (int i = 0; i < L - 1; ++i) {
-            const zrsrc_t rs = rs_of(p.o0[0] + kz0 + i - MID);
+            const rsrc_t rs = rs_of(p.o0[0] + kz0 + i - MID);
 #pragma unroll
             for (int k = 0; k < NPQ; ++k) z_load4<float>(rs, off[k], ring[i][k]);
             fix(ring[i]);
@@ -740,15 +707,15 @@ __global__ __launch_bounds__(1024) void gauss_zyx_dma_kernel(const float* __rest
         // slice of window position L - 1 of step kz0 into slot 0, of step kz0 + 1 into slot 1
         dma(p.o0[0] + kz0 + L - 1 - MID, 0);
         zwait_vm<0>();
-        z_lds_barrier();
+        lds_barrier();
         from_slot(0, pre);
         dma(p.o0[0] + kz0 + L - MID, 1);
         // NXP dropped stores, so that the first step's wait counts the same ops as every later
         // step's (the previous step's stores, then this step's pieces)
         {
-            const zrsrc_t none = z_rsrc(out, 0u);
+            const rsrc_t none = make_rsrc(out, 0u);
 #pragma unroll
-            for (int ip = 0; ip < NXP; ++ip) __builtin_amdgcn_raw_buffer_store_b32(0u, none, kZBad, 0, 2);
+            for (int ip = 0; ip < NXP; ++ip) __builtin_amdgcn_raw_buffer_store_b32(0u, none, kBadOff, 0, 2);
         }
         char* obase = reinterpret_cast<char*>(out) + o * onz * ony * onx * 4;
         for (int64_t kb = kz0; kb < kz1; kb += L) {
@@ -776,7 +743,7 @@ __global__ __launch_bounds__(1024) void gauss_zyx_dma_kernel(const float* __rest
                     if (k < NPQ - 1 || q < NQ)
                         *reinterpret_cast<float4*>(tile + 4 * q) = make_float4(sv[0], sv[1], sv[2], sv[3]);
                 }
-                z_lds_barrier();
+                lds_barrier();
                 // slot SL (read into pre during the previous step) is free: the slice of window
                 // position L - 1 two steps on (clamped; unused past the segment)
                 dma(p.o0[0] + kz + 2 + L - 1 - MID, SL);
@@ -800,9 +767,9 @@ __global__ __launch_bounds__(1024) void gauss_zyx_dma_kernel(const float* __rest
                 // own pieces of the next step's slice (issued a step ago, slot 1 - SL) landed:
                 // younger are the previous step's NXP stores and this step's pieces
                 if (three) zwait_vm<NXP + 3>(); else zwait_vm<NXP + 2>();
-                z_lds_barrier();
+                lds_barrier();
                 from_slot(1 - SL, pre);
-                const zrsrc_t ro = z_rsrc(obase + (kz < kz1 ? kz : 0) * ony * onx * 4,
+                const rsrc_t ro = make_rsrc(obase + (kz < kz1 ? kz : 0) * ony * onx * 4,
                                           kz < kz1 ? oplane_bytes : 0u);
 #pragma unroll
                 for (int ip = 0; ip < NXP; ++ip) {
@@ -824,13 +791,13 @@ __global__ __launch_bounds__(1024) void gauss_zyx_dma_kernel(const float* __rest
                     typedef unsigned int u4 __attribute__((ext_vector_type(4)));
                     const u4 q = {__float_as_uint(o4[0]), __float_as_uint(o4[1]),
                                   __float_as_uint(o4[2]), __float_as_uint(o4[3])};
-                    __builtin_amdgcn_raw_buffer_store_b128(q, ro, live && c0 < hx ? ooff : kZBad,
+                    __builtin_amdgcn_raw_buffer_store_b128(q, ro, live && c0 < hx ? ooff : kBadOff,
                                                            0, 2);
                 }
             });
         }
         zwait_vm<0>();  // no piece may land after the workgroup (or this volume) is done
-        z_lds_barrier();
+        lds_barrier();
     }
 }
 

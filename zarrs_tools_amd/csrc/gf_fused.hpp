@@ -12,6 +12,7 @@
 #include <type_traits>
 
 #include "zt_device.hpp"
+#include "zt_gpu.hpp"
 #include "zt_kernels.hpp"
 
 // Tuning knobs (tools/timek.hip sweeps them with -D; profiles/r02_ab_harness.txt). Variants that
@@ -205,12 +206,6 @@ __device__ __forceinline__ void tree_window_sums_t(const T (&in)[K + 2 * R], T (
     }
 }
 
-
-// Packed pair of f32 (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32: both lanes for one issue).
-typedef float f2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ f2 pk_fma(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
-
 // Window sums of W = 2R+1 consecutive values for K consecutive outputs sharing one core:
 // every window contains in[K-1 .. W-1], so out_i = (in[i..K-2]) + core + (in[W..W+i-1]) with
 // the left parts built as suffix sums and the right parts as prefix sums: W + 3K - 6 adds
@@ -219,11 +214,6 @@ __device__ __forceinline__ f2 pk_fma(f2 a, f2 b, f2 c) { return __builtin_elemen
 template <int R, int K, typename T>
 __device__ __forceinline__ void core_window_sums(const T (&in)[K + 2 * R], T (&out)[K]);
 
-__device__ __forceinline__ int clamped_count(int i, int n, int r) {
-    int lo = i - r < 0 ? 0 : i - r;
-    int hi = i + r > n - 1 ? n - 1 : i + r;
-    return hi - lo + 1;
-}
 // Product of window counts (each <= 2R + 1 <= 17, products <= 17^3): the full-rate 24-bit
 // multiply instead of v_mul_lo_u32.
 __device__ __forceinline__ int cmul(int a, int b) { return (int)__umul24((unsigned)a, (unsigned)b); }
@@ -258,15 +248,6 @@ __device__ __forceinline__ void core_window_sums(const T (&in)[K + 2 * R], T (&o
 #pragma unroll
         for (int i = 1; i < K - 1; ++i) out[i] = (left[i] + core) + right[i];
         out[K - 1] = core + right[K - 1];
-    }
-}
-
-// Compile-time loop: f(integral_constant<I>) for I in [B, E).
-template <int B, int E, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (B < E) {
-        f(std::integral_constant<int, B>{});
-        static_for<B + 1, E>(f);
     }
 }
 
@@ -327,64 +308,15 @@ template <typename T> struct S1 {
 template <> struct S1<uint8_t> { using acc = int; using in = int; static constexpr int HXB = 4; };
 template <> struct S1<uint16_t> { using acc = int; using in = int; static constexpr int HXB = 4; };
 
-// v_rcp_f32 flushes subnormals on both sides: the reciprocal of a d above 2^126 comes back as 0
-// (fast_div would return 0 where the quotient is near 1), that of a subnormal d as inf (NaN
-// after the correction). True for such a result (zero, subnormal or infinite), so one
-// v_cmp_class_f32 on the reciprocal tells whether d is inside [2^-126, 2^126].
-__device__ __forceinline__ bool rcp_unusable(float y) {
-    return __builtin_amdgcn_class(y, 0x2F4);  // -inf, -sub, -0, +0, +sub, +inf
-}
-
-// s / (s + eps): rcp + one Newton step + Markstein correction (6 VALU ops instead of the ~12 of
-// IEEE division; within 1 ulp, almost always correctly rounded). Special values follow IEEE:
-// 0/0 and inf/inf give NaN as in the reference. A d outside [2^-126, 2^126] (rcp_unusable)
-// takes the IEEE division, in a branch that tame data never enters.
-__device__ __forceinline__ float fast_div(float x, float d) {
-    float y = __builtin_amdgcn_rcpf(d);
-    if (__builtin_expect(rcp_unusable(y), 0)) return x / d;
-    float e = __builtin_fmaf(-d, y, 1.0f);
-    y = __builtin_fmaf(e, y, y);
-    float q = x * y;
-    float r = __builtin_fmaf(-d, q, x);
-    return __builtin_fmaf(r, y, q);
-}
-
-// Workgroup barrier for LDS hand-offs only. __syncthreads() also fences global memory, which
-// makes the compiler drain every outstanding global load (vmcnt(0)) — including the loads this
-// kernel keeps in flight across the barrier.
-__device__ __forceinline__ void lds_barrier() {
-    __asm__ volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-// x / d for an integer count d given rcp = RN(1/d): Markstein's correction step makes the
-// quotient correctly rounded (checked exhaustively-by-sampling for d <= 70000, tools/README),
-// so this equals IEEE division at 3 VALU ops instead of ~11.
-__device__ __forceinline__ float div_by_count(float x, float d, float rcp) {
-    float q = x * rcp;
-    float r = __builtin_fmaf(-q, d, x);
-    return __builtin_fmaf(r, rcp, q);
-}
-
-// ---- buffer (SRD) loads/stores: 32-bit byte offsets, hardware range check (an offset past
-//      num_records reads 0 / drops the store), no 64-bit address math per access. -----------
-using rsrc_t = __amdgpu_buffer_rsrc_t;
+// ---- buffer (SRD) loads/stores per element type (rsrc_t, make_rsrc, kBadOff: zt_gpu.hpp) ----
 #ifndef GF_OUT_AUX
 #define GF_OUT_AUX 2  // f32 output stores: 2 = nt (see Buf<float>::store)
 #endif
-constexpr int kBadOff = (int)0x80000000;  // >= num_records of any slice: reads 0, writes drop
-
-__device__ __forceinline__ rsrc_t make_rsrc(const void* base, uint32_t bytes) {
-    // Callers build descriptors only from kernel arguments and loop counters (wave-uniform
-    // scalars), so hipcc keeps them in SGPRs: no readfirstlane, no waterfall loops (T20).
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)bytes,
-                                             0x00020000);
-}
-
 template <typename T> struct Buf;
 template <> struct Buf<float> {
     template <int AUX = 0>
     __device__ static float load(rsrc_t r, int off) {
-        return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, AUX));
+        return load_f32<AUX>(r, off);
     }
     // Output stores are streamed with the non-temporal hint (aux 2 = nt) so they do not evict
     // the input slices the march re-reads from L2 a few steps later.
@@ -494,15 +426,7 @@ template <> struct Quad<uint8_t> {
     }
 };
 
-// Hide a value from the optimiser: keeps `ok ? off : kBadOff` a v_cndmask feeding one
-// unconditional buffer access (otherwise the select becomes an exec-masked branch around two
-// accesses, and the compiler's vmcnt accounting across the branch drains the loads in flight).
-__device__ __forceinline__ int opaque(int v) {
-    __asm__ volatile("" : "+v"(v));
-    return v;
-}
-
-// The same for a wave-uniform 64-bit value held in scalar registers.
+// opaque() for a wave-uniform 64-bit value held in scalar registers.
 __device__ __forceinline__ int64_t opaque_s(int64_t v) {
     __asm__ volatile("" : "+s"(v));
     return v;

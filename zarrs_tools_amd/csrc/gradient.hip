@@ -20,13 +20,13 @@
 #include <type_traits>
 
 #include "zt_device.hpp"
+#include "zt_gpu.hpp"
 #include "zt_kernels.hpp"
 
 namespace zt {
 
-// V: float, or a pair of floats (gfx950's packed f32 multiply / add: the same IEEE operations on
+// V: float, or a pair of floats f2 (gfx950's packed f32 multiply / add: the same IEEE operations on
 // two values per instruction; the fused march is bound by its vector arithmetic)
-typedef float gm_f2 __attribute__((ext_vector_type(2)));
 template <typename V>
 __device__ __forceinline__ V gm_tri(V a, V b, V c) {
     return (a * 0.25f + b * 0.5f) + c * 0.25f;  // kernel.rs:96-99
@@ -63,32 +63,14 @@ constexpr int kGMTH = kGMTy + 2, kGMMG = 4, kGMTP = kGMTx + 2 * kGMMG, kGMNQX = 
 constexpr int kGMNQ = kGMTH * kGMNQX, kGMNPQ = (kGMNQ + kGMNT - 1) / kGMNT;
 static_assert(kGMTy * kGMTx == 8 * kGMNT, "a thread makes 2 rows x 4 columns of outputs");
 
-// LDS hand-off barrier that leaves the global prefetch in flight (as gaussian.hip's)
-__device__ __forceinline__ void gm_lds_barrier() {
-    __asm__ volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
 // 4 consecutive elements from one 16/8/4-byte load (4/2/1-byte types)
 template <typename T>
 __device__ __forceinline__ void gm_load4(const T* p, float (&v)[4]) {
-    if constexpr (sizeof(T) == 4) {
-        const uint4 q = *reinterpret_cast<const uint4*>(p);
-        const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+    using U = typename UIntOf<sizeof(T)>::type;
+    U w[4];
+    load4_bits(reinterpret_cast<const U*>(p), w);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = Elem<T>::to_f32(__builtin_bit_cast(T, w[e]));
-    } else if constexpr (sizeof(T) == 2) {
-        const uint2 q = *reinterpret_cast<const uint2*>(p);
-        v[0] = Elem<T>::to_f32(__builtin_bit_cast(T, (uint16_t)(q.x & 0xffffu)));
-        v[1] = Elem<T>::to_f32(__builtin_bit_cast(T, (uint16_t)(q.x >> 16)));
-        v[2] = Elem<T>::to_f32(__builtin_bit_cast(T, (uint16_t)(q.y & 0xffffu)));
-        v[3] = Elem<T>::to_f32(__builtin_bit_cast(T, (uint16_t)(q.y >> 16)));
-    } else {
-        static_assert(sizeof(T) == 1, "quad loads of 1/2/4-byte elements");
-        const uint32_t q = *reinterpret_cast<const uint32_t*>(p);
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            v[e] = Elem<T>::to_f32(__builtin_bit_cast(T, (uint8_t)((q >> (8 * e)) & 0xffu)));
-    }
+    for (int e = 0; e < 4; ++e) v[e] = Elem<T>::to_f32(__builtin_bit_cast(T, w[e]));
 }
 
 template <typename TIn, bool QUAD>
@@ -145,7 +127,7 @@ __global__ __launch_bounds__(kGMNT) void gm_sobel3_kernel(const TIn* __restrict_
         }
     }
     // a staged quad is two pairs of x neighbours (packed f32 arithmetic)
-    auto ld = [&](int64_t zq, gm_f2 (&v)[NPQ][2]) {  // input slice zq (clamped to the block)
+    auto ld = [&](int64_t zq, f2 (&v)[NPQ][2]) {  // input slice zq (clamped to the block)
         zq = zq < 0 ? 0 : (zq > nz - 1 ? nz - 1 : zq);
         const TIn* sl = in + zq * plane;
 #pragma unroll
@@ -157,24 +139,24 @@ __global__ __launch_bounds__(kGMNT) void gm_sobel3_kernel(const TIn* __restrict_
 #pragma unroll
                 for (int e = 0; e < 4; ++e) w[e] = Elem<TIn>::to_f32(sl[off[4 * k + e]]);
             }
-            v[k][0] = gm_f2{w[0], w[1]};
-            v[k][1] = gm_f2{w[2], w[3]};
+            v[k][0] = f2{w[0], w[1]};
+            v[k][1] = f2{w[2], w[3]};
         }
     };
-    auto fix = [&](gm_f2 (&v)[NPQ][2]) {  // edge quads: the edge element broadcast
+    auto fix = [&](f2 (&v)[NPQ][2]) {  // edge quads: the edge element broadcast
         if constexpr (QUAD) {
             if (edgex) {
 #pragma unroll
                 for (int k = 0; k < NPQ; ++k) {
                     const bool l = (bl >> k) & 1, rr = (br >> k) & 1;
                     const float e = l ? v[k][0].x : v[k][1].y;
-                    if (l || rr) v[k][0] = v[k][1] = gm_f2{e, e};
+                    if (l || rr) v[k][0] = v[k][1] = f2{e, e};
                 }
             }
         }
     };
 
-    gm_f2 vm[NPQ][2], vc[NPQ][2], vp[NPQ][2], pre[NPQ][2];
+    f2 vm[NPQ][2], vc[NPQ][2], vp[NPQ][2], pre[NPQ][2];
     const int64_t zc0 = p.o0[0] + kz0;  // block slice of the segment's first output
     ld(zc0 - 1, vm);
     fix(vm);
@@ -194,7 +176,7 @@ __global__ __launch_bounds__(kGMNT) void gm_sobel3_kernel(const TIn* __restrict_
         float* dzw = dzb[buf];
 #pragma unroll
         for (int k = 0; k < NPQ; ++k) {
-            gm_f2 t2[2], d2[2];
+            f2 t2[2], d2[2];
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 t2[h] = gm_tri(vm[k][h], vc[k][h], vp[k][h]);
@@ -213,27 +195,27 @@ __global__ __launch_bounds__(kGMNT) void gm_sobel3_kernel(const TIn* __restrict_
         }
         // one barrier per step: this step's reads of buffer `buf` end before any thread passes
         // the next step's barrier, and only the step after that writes `buf` again
-        gm_lds_barrier();
+        lds_barrier();
         // staged rows r0 .. r0 + 3, window columns i = 0..5 = staged columns c0 + 3 .. c0 + 8
         // (output column c = staged column c + MG): element 3 of the thread's quad c0 / 4, the
         // quad after it, element 0 of the next; held as the pairs (1,2), (3,4), (0,5)
         constexpr int CO[6] = {3 * NQX, 1, NQX + 1, 2 * NQX + 1, 3 * NQX + 1, 2};
         constexpr int CA[3] = {1, 3, 0}, CB[3] = {2, 4, 5};
-        gm_f2 t[4][3], d[4][3];
+        f2 t[4][3], d[4][3];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const float* tr = tzw + (r0 + j) * TP + c0 / 4;
             const float* dr = dzw + (r0 + j) * TP + c0 / 4;
 #pragma unroll
             for (int pi = 0; pi < 3; ++pi) {
-                t[j][pi] = gm_f2{tr[CO[CA[pi]]], tr[CO[CB[pi]]]};
-                d[j][pi] = gm_f2{dr[CO[CA[pi]]], dr[CO[CB[pi]]]};
+                t[j][pi] = f2{tr[CO[CA[pi]]], tr[CO[CB[pi]]]};
+                d[j][pi] = f2{dr[CO[CA[pi]]], dr[CO[CB[pi]]]};
             }
         }
         // y passes on column pairs, then each column's two rows paired for the x passes
-        gm_f2 Ar[6], Br[6], Cr[6];
+        f2 Ar[6], Br[6], Cr[6];
         {
-            gm_f2 A[2][3], B[2][3], C[2][3];
+            f2 A[2][3], B[2][3], C[2][3];
 #pragma unroll
             for (int rr = 0; rr < 2; ++rr)
 #pragma unroll
@@ -244,21 +226,21 @@ __global__ __launch_bounds__(kGMNT) void gm_sobel3_kernel(const TIn* __restrict_
                 }
 #pragma unroll
             for (int pi = 0; pi < 3; ++pi) {
-                Ar[CA[pi]] = gm_f2{A[0][pi].x, A[1][pi].x};
-                Ar[CB[pi]] = gm_f2{A[0][pi].y, A[1][pi].y};
-                Br[CA[pi]] = gm_f2{B[0][pi].x, B[1][pi].x};
-                Br[CB[pi]] = gm_f2{B[0][pi].y, B[1][pi].y};
-                Cr[CA[pi]] = gm_f2{C[0][pi].x, C[1][pi].x};
-                Cr[CB[pi]] = gm_f2{C[0][pi].y, C[1][pi].y};
+                Ar[CA[pi]] = f2{A[0][pi].x, A[1][pi].x};
+                Ar[CB[pi]] = f2{A[0][pi].y, A[1][pi].y};
+                Br[CA[pi]] = f2{B[0][pi].x, B[1][pi].x};
+                Br[CB[pi]] = f2{B[0][pi].y, B[1][pi].y};
+                Cr[CA[pi]] = f2{C[0][pi].x, C[1][pi].x};
+                Cr[CB[pi]] = f2{C[0][pi].y, C[1][pi].y};
             }
         }
         float o4[2][4];
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            const gm_f2 gz = gm_tri(Ar[c], Ar[c + 1], Ar[c + 2]);  // axis 0
-            const gm_f2 gy = gm_tri(Br[c], Br[c + 1], Br[c + 2]);  // axis 1
-            const gm_f2 gx = gm_diff(Cr[c], Cr[c + 2]);            // axis 2
-            gm_f2 g = gz * gz;  // 0 + s * s == s * s
+            const f2 gz = gm_tri(Ar[c], Ar[c + 1], Ar[c + 2]);  // axis 0
+            const f2 gy = gm_tri(Br[c], Br[c + 1], Br[c + 2]);  // axis 1
+            const f2 gx = gm_diff(Cr[c], Cr[c + 2]);            // axis 2
+            f2 g = gz * gz;  // 0 + s * s == s * s
             g = g + gy * gy;
             g = g + gx * gx;
             o4[0][c] = sqrtf(g.x);

@@ -23,6 +23,7 @@
 
 #include "g4_limits.hpp"
 #include "zt_device.hpp"
+#include "zt_gpu.hpp"
 #include "zt_kernels.hpp"
 
 namespace zt {
@@ -51,21 +52,6 @@ template <typename TV> __device__ __forceinline__ TV zero_v();
 template <> __device__ __forceinline__ float zero_v<float>() { return 0.0f; }
 template <> __device__ __forceinline__ float2 zero_v<float2>() { return make_float2(0.0f, 0.0f); }
 
-// compile-time loop: f(integral_constant<I>) for I in [B, E)
-template <int B, int E, typename F>
-__device__ __forceinline__ void g4_static_for(F&& f) {
-    if constexpr (B < E) {
-        f(std::integral_constant<int, B>{});
-        g4_static_for<B + 1, E>(f);
-    }
-}
-
-__device__ __forceinline__ int ccount(int i, int n, int r) {
-    const int lo = i - r < 0 ? 0 : i - r;
-    const int hi = i + r > n - 1 ? n - 1 : i + r;
-    return hi - lo + 1;
-}
-
 #ifndef G4_BOX_TY
 #define G4_BOX_TY 16  // box3 march tile height (tools/timeg4rows.hip A/B)
 #endif
@@ -90,7 +76,7 @@ struct Str3 {
 // Measured slower on the T share (57.1-57.2 against 55.2-55.4 ms, profiles/r04_ldsbar_ab.jsonl).
 __device__ __forceinline__ void box3_barrier() {
 #if G4_LDS_BARRIER
-    __asm__ volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    lds_barrier();
 #else
     __syncthreads();
 #endif
@@ -274,12 +260,12 @@ __global__ __launch_bounds__(256) void g4_tab_kernel(double* __restrict__ U3T,
     const int64_t vol = (int64_t)nz * ny * nx;
     const int x = blockIdx.x * kPX + threadIdx.x, y = blockIdx.y * kPY + threadIdx.y;
     if (x >= nx || y >= ny) return;
-    const int cyx = ccount(y, ny, R) * ccount(x, nx, R);
+    const int cyx = clamped_count(y, ny, R) * clamped_count(x, nx, R);
     float2* TAB = reinterpret_cast<float2*>(U3T);
     const int tlo = t0 - R, thi = t0 + ont + R;  // (a, b) needed on [tlo, thi)
     for (int z = blockIdx.z; z < nz; z += gridDim.z) {
         const int64_t i = ((int64_t)z * ny + y) * nx + x;
-        const int c3 = ccount(z, nz, R) * cyx;
+        const int c3 = clamped_count(z, nz, R) * cyx;
         double U[TMAX];
 #pragma unroll
         for (int t = 0; t < TMAX; ++t) U[t] = t < T ? U3T[t * vol + i] : 0.0;
@@ -344,51 +330,10 @@ __global__ __launch_bounds__(256) void g4_tab_kernel(double* __restrict__ U3T,
 constexpr int kMX = 16, kMY = 16, kMZ = kG4TmarchTileZ;  // tile (x, y, z) (g4_limits.hpp)
 constexpr int kMVP = G4_TM_VP, kMNT = kMX * kMY * kMZ / kMVP;  // voxels per thread; threads
 
-// Buffer (SRD) accesses of the t-march: 32-bit byte offsets from a per-step base, out-of-range
-// offsets read 0 / drop the store, so the march has no branch around a memory instruction (the
-// compiler's vmcnt accounting then keeps the next step's loads in flight across the barriers).
-using g4rsrc = __amdgpu_buffer_rsrc_t;
+// The t-march's memory accesses go through buffer descriptors (zt_gpu.hpp): 32-bit byte offsets
+// from a per-step base, kBadOff outside the block.
 typedef unsigned int u32x2g4 __attribute__((ext_vector_type(2)));
-constexpr int kG4Bad = (int)0x80000000;
-__device__ __forceinline__ g4rsrc g4_rsrc(const void* base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)bytes,
-                                             0x00020000);
-}
-__device__ __forceinline__ float g4_ld(g4rsrc r, int off) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0));
-}
-// LDS-only workgroup barrier (__syncthreads would also wait for the loads in flight)
-__device__ __forceinline__ void g4_lds_barrier() {
-    __asm__ volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-__device__ __forceinline__ int g4_opaque(int v) {
-    __asm__ volatile("" : "+v"(v));
-    return v;
-}
-
 // g4_tmarch_offsets_fit (g4_limits.hpp): the host check of the t-march's 32-bit offsets.
-
-// x / d for an integer count d given rcp = RN(1/d): Markstein's correction makes the quotient
-// correctly rounded (= IEEE division) in 3 VALU ops (as gf_fused.hpp's div_by_count).
-__device__ __forceinline__ float g4_div_by_count(float x, float d, float rcp) {
-    const float q = x * rcp;
-    const float r = __builtin_fmaf(-q, d, x);
-    return __builtin_fmaf(r, rcp, q);
-}
-// s / (s + eps): rcp, one Newton step and Markstein's correction (within 1 ulp, almost always
-// correctly rounded; 0/0 gives NaN as in the reference), as gf_fused.hpp's fast_div. v_rcp_f32
-// flushes subnormals: the reciprocal of a d above 2^126 comes back as 0, that of a subnormal d
-// as inf; such a result (one v_cmp_class_f32) sends the element to the IEEE division.
-__device__ __forceinline__ float g4_fast_div(float x, float d) {
-    float y = __builtin_amdgcn_rcpf(d);
-    if (__builtin_expect(__builtin_amdgcn_class(y, 0x2F4), 0))  // -inf, -sub, -0, +0, +sub, +inf
-        return x / d;
-    const float e = __builtin_fmaf(-d, y, 1.0f);
-    y = __builtin_fmaf(e, y, y);
-    const float q = x * y;
-    const float r = __builtin_fmaf(-d, q, x);
-    return __builtin_fmaf(r, y, q);
-}
 
 template <int R>
 __global__ __launch_bounds__(kMNT) void g4_tmarch_tab_kernel(const float* __restrict__ v, Str3 vs,
@@ -413,7 +358,7 @@ __global__ __launch_bounds__(kMNT) void g4_tmarch_tab_kernel(const float* __rest
     constexpr int W4 = (2 * R + 1) * (2 * R + 1) * (2 * R + 1) * (2 * R + 1);
     __shared__ float rtab[W4 + 1];
     for (int c = threadIdx.x; c <= W4; c += kMNT) rtab[c] = c > 0 ? 1.0f / (float)c : 0.0f;
-    g4_lds_barrier();
+    lds_barrier();
 
     // XCD-aware block order (xcd_block): each XCD marches a contiguous run of neighbouring tiles
     const int64_t nb = gridDim.x;
@@ -427,7 +372,7 @@ __global__ __launch_bounds__(kMNT) void g4_tmarch_tab_kernel(const float* __rest
     // element; reading each x-pass item's row segment straight from global memory instead, 1.6x
     // the load instructions, measured 1.35x slower: profiles/r05_tmarch_ab.txt). Byte offsets
     // from plane z0 - R of a timepoint, shifted up to plane 0 when that plane lies below the
-    // block (buffer bases must not precede the allocation); kG4Bad outside the block (reads 0:
+    // block (buffer bases must not precede the allocation); kBadOff outside the block (reads 0:
     // the zero padding of the clamped windows).
     const int zsh = min(z0 - R, 0);
     const int64_t vbase = (int64_t)(z0 - R - zsh) * vs.z;
@@ -438,10 +383,10 @@ __global__ __launch_bounds__(kMNT) void g4_tmarch_tab_kernel(const float* __rest
         const int ez = e / (SY * SX), ey = (e / SX) % SY, ex = e % SX;
         const int gz = z0 - R + ez, gy = y0 - R + ey, gx = x0 - R + ex;
         const bool in = e < NS && gz >= 0 && gz < nz && gy >= 0 && gy < ny && gx >= 0 && gx < nx;
-        soff[k] = in ? (int)(((ez + zsh) * vs.z + gy * vs.y + gx) * 4) : kG4Bad;
+        soff[k] = in ? (int)(((ez + zsh) * vs.z + gy * vs.y + gx) * 4) : kBadOff;
     }
-    // (soff, voff and toff are step-invariant registers with kG4Bad already selected, so the
-    //  accesses take them as they are: passing them through g4_opaque added a register copy per
+    // (soff, voff and toff are step-invariant registers with kBadOff already selected, so the
+    //  accesses take them as they are: passing them through opaque added a register copy per
     //  access, 1 % of the T share, profiles/r06_plain_offsets.txt)
     // staged values of steps t + 1 .. t + PFD (pre[0 .. PFD - 1]): the loads of a step stay in
     // flight for PFD steps
@@ -449,9 +394,9 @@ __global__ __launch_bounds__(kMNT) void g4_tmarch_tab_kernel(const float* __rest
     float pre[PFD][NPS];
     auto load_stage = [&](float (&dst)[NPS], int t) {
         const bool ok = (unsigned)t < (unsigned)T;
-        const g4rsrc r = g4_rsrc(v + (ok ? (int64_t)t * vs.t + vbase : 0), ok ? 0x7FFFFFF0u : 0u);
+        const rsrc_t r = make_rsrc(v + (ok ? (int64_t)t * vs.t + vbase : 0), ok ? 0x7FFFFFF0u : 0u);
 #pragma unroll
-        for (int k = 0; k < NPS; ++k) dst[k] = g4_ld(r, soff[k]);
+        for (int k = 0; k < NPS; ++k) dst[k] = load_f32(r, soff[k]);
     };
 
     // this thread's voxels: (x, y) and VP consecutive z
@@ -464,9 +409,9 @@ __global__ __launch_bounds__(kMNT) void g4_tmarch_tab_kernel(const float* __rest
     for (int q = 0; q < VP; ++q) {
         const int gz = z0 + lz + q;
         own[q] = gx < xend && gy < yend && gz < zend;
-        c3[q] = ccount(gz, nz, R) * ccount(gy, ny, R) * ccount(gx, nx, R);
-        toff[q] = own[q] ? (((lz + q) * ny + gy) * nx + gx) * 8 : kG4Bad;
-        voff[q] = own[q] ? (int)(((lz + q) * vs.z + gy * vs.y + gx) * 4) : kG4Bad;
+        c3[q] = clamped_count(gz, nz, R) * clamped_count(gy, ny, R) * clamped_count(gx, nx, R);
+        toff[q] = own[q] ? (((lz + q) * ny + gy) * nx + gx) * 8 : kBadOff;
+        voff[q] = own[q] ? (int)(((lz + q) * vs.z + gy * vs.y + gx) * 4) : kBadOff;
     }
     const int64_t vol = (int64_t)nz * ny * nx;
     const int tlo = t0 - R, thi = t0 + ont + R;  // (a, b) needed on [tlo, thi)
@@ -489,7 +434,7 @@ __global__ __launch_bounds__(kMNT) void g4_tmarch_tab_kernel(const float* __rest
 #pragma unroll
     for (int d = 0; d < PFD; ++d) load_stage(pre[d], tb + d);
     for (int tb0 = tb; tb0 < tb + nsteps; tb0 += W) {
-        g4_static_for<0, W>([&](auto kc) {
+        static_for<0, W>([&](auto kc) {
             constexpr int k = decltype(kc)::value;
             const int t = tb0 + k;
             const int tau = t - R;  // (a, b) of this step
@@ -498,10 +443,10 @@ __global__ __launch_bounds__(kMNT) void g4_tmarch_tab_kernel(const float* __rest
             float vt[VP];
             {
                 const bool ok = (unsigned)tau < (unsigned)T;
-                const g4rsrc r = g4_rsrc(v + (ok ? (int64_t)tau * vs.t + (int64_t)z0 * vs.z : 0),
+                const rsrc_t r = make_rsrc(v + (ok ? (int64_t)tau * vs.t + (int64_t)z0 * vs.z : 0),
                                          ok ? 0x7FFFFFF0u : 0u);
 #pragma unroll
-                for (int q = 0; q < VP; ++q) vt[q] = g4_ld(r, voff[q]);
+                for (int q = 0; q < VP; ++q) vt[q] = load_f32(r, voff[q]);
             }
             double u3[VP];
 #pragma unroll
@@ -518,7 +463,7 @@ __global__ __launch_bounds__(kMNT) void g4_tmarch_tab_kernel(const float* __rest
                 for (int j = 0; j < NPS; ++j) pre[d][j] = pre[d + 1][j];
             load_stage(pre[PFD - 1], t + PFD);
             if (t < te) {
-            g4_lds_barrier();
+            lds_barrier();
             for (int it = threadIdx.x; it < NXI; it += kMNT) {  // x-window sums (exact f64)
                 const int row = it / (kMX / KX), sx = (it % (kMX / KX)) * KX;
                 const float* src = &Vs[0][0][0] + row * SX + sx;
@@ -534,7 +479,7 @@ __global__ __launch_bounds__(kMNT) void g4_tmarch_tab_kernel(const float* __rest
                     dst[j] = s;
                 }
             }
-            g4_lds_barrier();
+            lds_barrier();
             for (int it = threadIdx.x; it < NYI; it += kMNT) {  // y-window sums, lanes on x
                 const int xx = it % kMX, sy = ((it / kMX) % (kMY / KY)) * KY,
                           ez = it / (kMX * (kMY / KY));
@@ -549,7 +494,7 @@ __global__ __launch_bounds__(kMNT) void g4_tmarch_tab_kernel(const float* __rest
                     Ys[ez][sy + j][xx] = s;
                 }
             }
-            g4_lds_barrier();
+            lds_barrier();
             {  // z-window sums of this thread's VP voxels (exact f64)
                 double zs[VP + 2 * R];
 #pragma unroll
@@ -571,7 +516,7 @@ __global__ __launch_bounds__(kMNT) void g4_tmarch_tab_kernel(const float* __rest
             const bool need_ab = tau >= tlo && tau < thi && tau >= 0 && tau < T;
             const int ct = min(tau + R, T - 1) - max(tau - R, 0) + 1;
             const bool emit = tp >= t0 && tp < t0 + ont;
-            const g4rsrc rt = g4_rsrc(TAB + (emit ? (int64_t)(tp - t0) * vol + (int64_t)z0 * ny * nx : 0),
+            const rsrc_t rt = make_rsrc(TAB + (emit ? (int64_t)(tp - t0) * vol + (int64_t)z0 * ny * nx : 0),
                                       emit ? 0x7FFFFFF0u : 0u);
 #pragma unroll
             for (int q = 0; q < VP; ++q) {
@@ -582,10 +527,10 @@ __global__ __launch_bounds__(kMNT) void g4_tmarch_tab_kernel(const float* __rest
                 // u = RN(U4) / c (summed_area_table_mean: Markstein = IEEE division); a within
                 // 1 ulp (IEEE divisions here: 1.2 % slower, profiles/r06_tmarch_fastdiv.txt)
                 const int ci = c3[q] * ct;
-                const float u = g4_div_by_count((float)U4, (float)ci, rtab[ci]);
+                const float u = div_by_count((float)U4, (float)ci, rtab[ci]);
                 const float d = vt[q] - u;
                 const float sq = d * d;  // (v - u).powf(2.0)
-                const float a = g4_fast_div(sq, sq + eps);
+                const float a = fast_div(sq, sq + eps);
                 const float2 ab = need_ab ? make_float2(a, (1.0f - a) * u) : make_float2(0.f, 0.f);
                 SA[q] += (double)ab.x;
                 SB[q] += (double)ab.y;
@@ -677,27 +622,27 @@ __global__ __launch_bounds__(RING ? kTX * TYF / 2 : kNT) void box3_final_kernel(
     }
     float2* const Zf = &Z[0][0];
     // F32: the byte offsets of the owned apron points, this thread's v loads and output stores,
-    // selected once (kG4Bad outside) and used as they are at every access
+    // selected once (kBadOff outside) and used as they are at every access
     int boff[NPT], vof[KY], oof[KY];
     if constexpr (F32) {
 #pragma unroll
-        for (int k = 0; k < NPT; ++k) boff[k] = pidx[k] >= 0 ? (int)pidx[k] * 8 : kG4Bad;
+        for (int k = 0; k < NPT; ++k) boff[k] = pidx[k] >= 0 ? (int)pidx[k] * 8 : kBadOff;
         const int tx = threadIdx.x % kTX, sy = (threadIdx.x / kTX) * KY;
         const int gx = x0 + tx;
 #pragma unroll
         for (int j = 0; j < KY; ++j) {
             const int gy = y0 + sy + j;
             const bool in = gx < ox1 && gy < oy1;
-            vof[j] = in ? (int)((gy * vs.y + gx) * 4) : kG4Bad;
-            oof[j] = in ? (int)(((gy - oy0) * g.out_strides[2] + (gx - ox0)) * 4) : kG4Bad;
+            vof[j] = in ? (int)((gy * vs.y + gx) * 4) : kBadOff;
+            oof[j] = in ? (int)(((gy - oy0) * g.out_strides[2] + (gx - ox0)) * 4) : kBadOff;
         }
     }
-    // (selected at the access instead, through g4_opaque: box3_final 14.20 against 14.08 ms,
+    // (selected at the access instead, through opaque: box3_final 14.20 against 14.08 ms,
     //  profiles/r06_plain_offsets.txt)
     auto load = [&](int z, int k) -> float2 {
         if constexpr (F32) {
             const bool ok = (unsigned)z < (unsigned)nz;
-            const g4rsrc r = g4_rsrc(vol + (ok ? (int64_t)z * plane : 0), ok ? 0x7FFFFFF0u : 0u);
+            const rsrc_t r = make_rsrc(vol + (ok ? (int64_t)z * plane : 0), ok ? 0x7FFFFFF0u : 0u);
             const u32x2g4 q = __builtin_amdgcn_raw_buffer_load_b64(r, boff[k], 0, 0);
             return make_float2(__uint_as_float(q.x), __uint_as_float(q.y));
         } else {
@@ -706,7 +651,7 @@ __global__ __launch_bounds__(RING ? kTX * TYF / 2 : kNT) void box3_final_kernel(
         }
     };
     auto step_barrier = [] {
-        if constexpr (F32) g4_lds_barrier();
+        if constexpr (F32) lds_barrier();
         else box3_barrier();
     };
     // F32: v of this thread's outputs of step z, loaded before the step's TAB prefetch so that
@@ -714,10 +659,10 @@ __global__ __launch_bounds__(RING ? kTX * TYF / 2 : kNT) void box3_final_kernel(
     auto v_load = [&](int z, float (&vv)[KY]) {
         if constexpr (F32) {
             const bool zok = z < z1;
-            const g4rsrc rv = g4_rsrc(v + (zok ? t * vs.t + (int64_t)z * vs.z : 0),
+            const rsrc_t rv = make_rsrc(v + (zok ? t * vs.t + (int64_t)z * vs.z : 0),
                                       zok ? 0x7FFFFFF0u : 0u);
 #pragma unroll
-            for (int j = 0; j < KY; ++j) vv[j] = g4_ld(rv, vof[j]);
+            for (int j = 0; j < KY; ++j) vv[j] = load_f32(rv, vof[j]);
         }
     };
     // x / y windows of the Z slice of output slice z and the final stage
@@ -739,7 +684,7 @@ __global__ __launch_bounds__(RING ? kTX * TYF / 2 : kNT) void box3_final_kernel(
         step_barrier();
         const int tx = threadIdx.x % kTX, sy = (threadIdx.x / kTX) * KY;
         const int gx = x0 + tx;
-        const int czx = ccount(min(z, nz - 1), nz, R) * ccount(gx, nx, R) * ct;
+        const int czx = clamped_count(min(z, nz - 1), nz, R) * clamped_count(gx, nx, R) * ct;
         float2 sacc = make_float2(0.f, 0.f);
 #pragma unroll
         for (int j = 0; j <= 2 * R; ++j) acc_add(sacc, X[sy + j][tx]);
@@ -754,17 +699,17 @@ __global__ __launch_bounds__(RING ? kTX * TYF / 2 : kNT) void box3_final_kernel(
                 // z past the segment (padded steps): zero-record descriptors, nothing stored
                 const bool zok = z < z1;
                 const bool in = gx < ox1 && gy < oy1;
-                const float cnt = (float)(czx * ccount(min(gy, ny - 1), ny, R));
+                const float cnt = (float)(czx * clamped_count(min(gy, ny - 1), ny, R));
                 const float ma = (float)sacc.x / cnt, mb = (float)sacc.y / cnt;
                 const float o = __fadd_rn(__fmul_rn(vvp[j], ma), mb);  // v *= ma; v += mb
-                const g4rsrc ro = g4_rsrc(
+                const rsrc_t ro = make_rsrc(
                     static_cast<float*>(out) +
                         (zok ? ot * g.out_strides[0] + (int64_t)(z - oz0) * g.out_strides[1] : 0),
                     zok ? 0x7FFFFFF0u : 0u);
                 (void)in;
                 __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o), ro, oof[j], 0, 2);
             } else if (gx < ox1 && gy < oy1) {
-                const float cnt = (float)(czx * ccount(gy, ny, R));
+                const float cnt = (float)(czx * clamped_count(gy, ny, R));
                 const float ma = (float)sacc.x / cnt, mb = (float)sacc.y / cnt;
                 const float vv = v[t * vs.t + (int64_t)z * vs.z + (int64_t)gy * vs.y + gx];
                 const float o = __fadd_rn(__fmul_rn(vv, ma), mb);  // v *= ma; v += mb

@@ -45,6 +45,7 @@
 #include <type_traits>
 
 #include "zt_device.hpp"
+#include "zt_gpu.hpp"
 #include "zt_kernels.hpp"
 #include "zt_labels_host.hpp"
 
@@ -63,11 +64,6 @@ constexpr uint32_t kLblFlushTiles = 1u << 20;
 constexpr int kLblMaxTableBytes = 40 * 1024;
 static_assert(T % kWaves == 0, "a wave owns whole rows of a tile");
 
-template <int ESZ> struct UIntOf;
-template <> struct UIntOf<1> { using type = uint8_t; };
-template <> struct UIntOf<2> { using type = uint16_t; };
-template <> struct UIntOf<4> { using type = uint32_t; };
-template <> struct UIntOf<8> { using type = uint64_t; };
 
 struct LblGeom {
     int64_t dim[kMaxDims];  // the box, padded in front with unit axes

@@ -19,28 +19,16 @@
 #include <algorithm>
 
 #include "zt_device.hpp"
+#include "zt_gpu.hpp"
 #include "zt_kernels.hpp"
 
 namespace zt {
 
-// storage bits <-> order key of width K; mode: kRankKeyUnsigned / Signed / Float
-template <typename K>
-__device__ __forceinline__ K rk_to_key(K b, int mode) {
-    constexpr K S = (K)((K)1 << (8 * sizeof(K) - 1));
-    const K f = (b & S) ? (K)~(K)0 : S;
-    return (K)(b ^ (mode == kRankKeyFloat ? f : (mode == kRankKeySigned ? S : (K)0)));
-}
-template <typename K>
-__device__ __forceinline__ K rk_from_key(K k, int mode) {
-    constexpr K S = (K)((K)1 << (8 * sizeof(K) - 1));
-    const K f = (k & S) ? S : (K)~(K)0;
-    return (K)(k ^ (mode == kRankKeyFloat ? f : (mode == kRankKeySigned ? S : (K)0)));
-}
-
-// The same conversions on a key widened to 32 bits, for the fused kernel: with S the sign bit of
-// the W-bit element, xs = S for signed and float elements (else 0) and xf = S - 1 for float
-// elements (else 0), both made on the host: key = b ^ xs ^ (b negative ? xf : 0), and the same
-// two steps in the other order turn a key back (the sign of key ^ xs is the element's sign).
+// to_order_key / from_order_key (zt_gpu.hpp) on a key widened to 32 bits, for the fused kernel:
+// with S the sign bit of the W-bit element, xs = S for signed and float elements (else 0) and
+// xf = S - 1 for float elements (else 0), both made on the host: key = b ^ xs ^ (b negative ? xf
+// : 0), and the same two steps in the other order turn a key back (the sign of key ^ xs is the
+// element's sign).
 template <int W>
 __device__ __forceinline__ uint32_t rk_key32(uint32_t b, uint32_t xs, uint32_t xf) {
     return b ^ xs ^ ((uint32_t)((int32_t)(b << (32 - W)) >> 31) & xf);
@@ -51,19 +39,17 @@ __device__ __forceinline__ uint32_t rk_unkey32(uint32_t k, uint32_t xs, uint32_t
     return t ^ ((uint32_t)((int32_t)(t << (32 - W)) >> 31) & xf);
 }
 
-__device__ __forceinline__ uint32_t rk_min(uint32_t a, uint32_t b) { return a < b ? a : b; }
-__device__ __forceinline__ uint32_t rk_max(uint32_t a, uint32_t b) { return a > b ? a : b; }
 __device__ __forceinline__ uint32_t rk_min3(uint32_t a, uint32_t b, uint32_t c) {
-    return rk_min(rk_min(a, b), c);
+    return kmin(kmin(a, b), c);
 }
 __device__ __forceinline__ uint32_t rk_max3(uint32_t a, uint32_t b, uint32_t c) {
-    return rk_max(rk_max(a, b), c);
+    return kmax(kmax(a, b), c);
 }
 __device__ __forceinline__ uint32_t rk_med3(uint32_t a, uint32_t b, uint32_t c) {
-    return rk_max(rk_min(a, b), rk_min(rk_max(a, b), c));
+    return kmax(kmin(a, b), kmin(kmax(a, b), c));
 }
 __device__ __forceinline__ void rk_cx(uint32_t& a, uint32_t& b) {  // compare-exchange
-    const uint32_t lo = rk_min(a, b), hi = rk_max(a, b);
+    const uint32_t lo = kmin(a, b), hi = kmax(a, b);
     a = lo;
     b = hi;
 }
@@ -125,29 +111,6 @@ constexpr int kRKNPQ = (kRKNQ + kRKNT - 1) / kRKNT;  // staged quads per thread
 constexpr int kRKNP = 4 * kRKNPQ;                    // staged points per thread
 constexpr int kRKRows = kRKTy * kRKTx / kRKNT;       // output rows per thread
 static_assert(kRKNT % kRKTx == 0 && kRKRows * (kRKNT / kRKTx) == kRKTy, "thread -> column strip");
-
-// LDS hand-off barrier that leaves the global prefetch in flight (as gradient.hip's)
-__device__ __forceinline__ void rk_lds_barrier() {
-    __asm__ volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-// 4 consecutive elements' storage bits from one 16/8/4-byte load (4/2/1-byte elements)
-template <typename K>
-__device__ __forceinline__ void rk_load4(const K* p, K (&v)[4]) {
-    if constexpr (sizeof(K) == 4) {
-        const uint4 q = *reinterpret_cast<const uint4*>(p);
-        v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
-    } else if constexpr (sizeof(K) == 2) {
-        const uint2 q = *reinterpret_cast<const uint2*>(p);
-        v[0] = (K)(q.x & 0xffffu), v[1] = (K)(q.x >> 16);
-        v[2] = (K)(q.y & 0xffffu), v[3] = (K)(q.y >> 16);
-    } else {
-        static_assert(sizeof(K) == 1, "quad loads of 1/2/4-byte elements");
-        const uint32_t q = *reinterpret_cast<const uint32_t*>(p);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = (K)((q >> (8 * e)) & 0xffu);
-    }
-}
 
 template <typename K, int KIND, bool QUAD>
 __global__ __launch_bounds__(kRKNT) void rank3_kernel(const K* __restrict__ in,
@@ -216,7 +179,7 @@ __global__ __launch_bounds__(kRKNT) void rank3_kernel(const K* __restrict__ in,
         for (int k = 0; k < NPQ; ++k) {
             K w[4];
             if constexpr (QUAD) {
-                rk_load4<K>(sl + off[k], w);
+                load4_bits<K>(sl + off[k], w);
             } else {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) w[e] = sl[off[4 * k + e]];
@@ -292,7 +255,7 @@ __global__ __launch_bounds__(kRKNT) void rank3_kernel(const K* __restrict__ in,
         }
         // two buffers, one barrier per step: this step's reads of buffer `buf` end before any
         // thread passes the next step's barrier, and only the step after that writes `buf` again
-        rk_lds_barrier();
+        lds_barrier();
         K* dst = out + (kz * ony + y0 + r0) * onx + x0 + cx;
         if constexpr (KIND != kRankMedian) {
             const uint32_t* L = lds[buf][0] + r0 * TW + cx + MG - 1;
@@ -331,7 +294,7 @@ __global__ __launch_bounds__(kRKNT) void rank3_kernel(const K* __restrict__ in,
 #pragma unroll
                 for (int j = 0; j < 18; ++j) w[j] = w[j + 9];
             }
-            rk_lds_barrier();  // one buffer: every read ends before the next step's writes
+            lds_barrier();  // one buffer: every read ends before the next step's writes
         }
 #pragma unroll
         for (int k = 0; k < NP; ++k) {
@@ -439,12 +402,12 @@ __global__ __launch_bounds__(256) void rank_pass_kernel(const K* __restrict__ in
         const int64_t lo = o0 + k - h < 0 ? 0 : o0 + k - h;
         const int64_t hi = o0 + k + h > n - 1 ? n - 1 : o0 + k + h;
         const K* src = in + o * n * inner + c;
-        K acc = rk_to_key<K>(src[lo * inner], mode);
+        K acc = to_order_key<K>(src[lo * inner], mode);
         for (int64_t j = lo + 1; j <= hi; ++j) {
-            const K v = rk_to_key<K>(src[j * inner], mode);
+            const K v = to_order_key<K>(src[j * inner], mode);
             acc = MAX ? (v > acc ? v : acc) : (v < acc ? v : acc);
         }
-        out[i] = rk_from_key<K>(acc, mode);
+        out[i] = from_order_key<K>(acc, mode);
     }
 }
 
@@ -533,12 +496,12 @@ __global__ __launch_bounds__(256) void rank_median_kernel(const K* __restrict__ 
                 const K* row = in + base;
                 for (int64_t x = xlo; x <= xhi; ++x) {
                     const int64_t xc = x < 0 ? 0 : (x > nl - 1 ? nl - 1 : x);
-                    below += rk_to_key<K>(row[xc], mode) < cand ? 1 : 0;
+                    below += to_order_key<K>(row[xc], mode) < cand ? 1 : 0;
                 }
             }
             if (below <= p.rank) res = cand;
         }
-        out[i] = rk_from_key<K>(res, mode);
+        out[i] = from_order_key<K>(res, mode);
     }
 }
 

@@ -6,7 +6,7 @@
 // neighbours as the labelling's (coordinates differ by at most 1 on every axis and on at most
 // `connectivity` axes, nothing wraps). By erosion: the same with the order reversed. Elements are
 // only ever selected under the rank filters' total order: storage bits become an unsigned key at
-// every load (rank.hip's mapping; for erosion the key is complemented, which turns erosion into
+// every load (to_order_key; for erosion the key is complemented, which turns erosion into
 // the dilation below) and a key becomes storage bits again at every store.
 //
 //   rec_init_kernel<ESZ>   J0 into the first working buffer: min(marker, mask), or a marker made
@@ -29,6 +29,7 @@
 #include <type_traits>
 
 #include "zt_device.hpp"
+#include "zt_gpu.hpp"
 #include "zt_kernels.hpp"
 
 namespace zt {
@@ -40,31 +41,6 @@ constexpr int AZ = TZ + 2, AY = TY + 2, AX = TX + 2;  // the tile with its apron
 constexpr int kThreads = TY * TX;                     // one thread per (y, x) column of the tile
 constexpr int kInitThreads = 256;
 static_assert(kThreads == 256, "four waves per workgroup");
-
-template <int ESZ> struct UIntOf;
-template <> struct UIntOf<1> { using type = uint8_t; };
-template <> struct UIntOf<2> { using type = uint16_t; };
-template <> struct UIntOf<4> { using type = uint32_t; };
-template <> struct UIntOf<8> { using type = uint64_t; };
-
-// storage bits <-> working key: the rank filters' order key (rk_to_key / rk_from_key in rank.hip),
-// xor `comp` (all ones for erosion, 0 for dilation)
-template <typename K>
-__device__ __forceinline__ K rec_to_key(K b, int mode, K comp) {
-    constexpr K S = (K)((K)1 << (8 * sizeof(K) - 1));
-    const K f = (b & S) ? (K)~(K)0 : S;
-    return (K)(b ^ (mode == kRankKeyFloat ? f : (mode == kRankKeySigned ? S : (K)0)) ^ comp);
-}
-template <typename K>
-__device__ __forceinline__ K rec_from_key(K k, int mode, K comp) {
-    constexpr K S = (K)((K)1 << (8 * sizeof(K) - 1));
-    k = (K)(k ^ comp);
-    const K f = (k & S) ? S : (K)~(K)0;
-    return (K)(k ^ (mode == kRankKeyFloat ? f : (mode == kRankKeySigned ? S : (K)0)));
-}
-
-template <typename K> __device__ __forceinline__ K kmin(K a, K b) { return a < b ? a : b; }
-template <typename K> __device__ __forceinline__ K kmax(K a, K b) { return a > b ? a : b; }
 
 // ---- the generated h marker: (mask as f64 -/+ h) as T, the arithmetic filter's casts ------------
 
@@ -123,10 +99,10 @@ __device__ __forceinline__ typename UIntOf<ESZ>::type rec_init_one(
     typename UIntOf<ESZ>::type marker_bits) {
     using K = typename UIntOf<ESZ>::type;
     const K comp = g.erosion ? (K)~(K)0 : (K)0;
-    const K km = rec_to_key<K>(mask_bits, g.key_mode, comp);
+    const K km = to_order_key<K>(mask_bits, g.key_mode, comp);
     K j;
     if (g.marker_mode == kRecMarker) {
-        j = kmin(rec_to_key<K>(marker_bits, g.key_mode, comp), km);
+        j = kmin(to_order_key<K>(marker_bits, g.key_mode, comp), km);
     } else if (g.marker_mode == kRecFillHoles) {
         bool border = g.all_border != 0;
         if (!border) {
@@ -138,9 +114,9 @@ __device__ __forceinline__ typename UIntOf<ESZ>::type rec_init_one(
         j = border ? km : (K)0;  // the greatest key of the type, complemented
     } else {
         const K shifted = (K)rec_shift<ESZ>(g.dtype, (uint64_t)mask_bits, g.h);
-        j = kmin(rec_to_key<K>(shifted, g.key_mode, comp), km);
+        j = kmin(to_order_key<K>(shifted, g.key_mode, comp), km);
     }
-    return rec_from_key<K>(j, g.key_mode, comp);
+    return from_order_key<K>(j, g.key_mode, comp);
 }
 
 // 16 bytes per lane when every pointer is 16-byte aligned (the tail, fewer than 16 / ESZ elements,
@@ -212,7 +188,7 @@ __global__ __launch_bounds__(kThreads) void rec_round_kernel(const RecRound g) {
         const int64_t z = z0 + az - 1, y = y0 + ay - 1, x = x0 + ax - 1;
         K k = 0;
         if (z >= 0 && z < g.Z && y >= 0 && y < g.Y && x >= 0 && x < g.X)
-            k = rec_to_key<K>(src[(z * g.Y + y) * g.X + x], g.key_mode, comp);
+            k = to_order_key<K>(src[(z * g.Y + y) * g.X + x], g.key_mode, comp);
         sj[i] = k;
     }
     // this thread's column (ly, lx), z = 0 .. TZ - 1: mask keys (the least key outside the array,
@@ -225,7 +201,7 @@ __global__ __launch_bounds__(kThreads) void rec_round_kernel(const RecRound g) {
     for (int z = 0; z < TZ; ++z) {
         m[z] = 0;
         if (in_xy && z0 + z < g.Z)
-            m[z] = rec_to_key<K>(mask[((z0 + z) * g.Y + gy) * g.X + gx], g.key_mode, comp);
+            m[z] = to_order_key<K>(mask[((z0 + z) * g.Y + gy) * g.X + gx], g.key_mode, comp);
     }
     __syncthreads();
     const int base = (ly + 1) * AX + (lx + 1);  // the column's (y, x) in a plane of sj
@@ -281,7 +257,7 @@ __global__ __launch_bounds__(kThreads) void rec_round_kernel(const RecRound g) {
 #pragma unroll
         for (int z = 0; z < TZ; ++z)
             if (z0 + z < g.Z)
-                dst[((z0 + z) * g.Y + gy) * g.X + gx] = rec_from_key<K>(cur[z], g.key_mode, comp);
+                dst[((z0 + z) * g.Y + gy) * g.X + gx] = from_order_key<K>(cur[z], g.key_mode, comp);
     }
     if (tile_changed && tid == 0) atomicOr(g.flag, 1u);
 }

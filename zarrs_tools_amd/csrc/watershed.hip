@@ -2,7 +2,7 @@
 // filter).
 //
 // Every element of the domain D gets the label of one seed. Elements are compared only through the
-// rank filters' order key (rank.hip's mapping; complemented when the relief is flooded from its
+// rank filters' order key (to_order_key; complemented when the relief is flooded from its
 // maxima): the flood key. Four steps, each a pure function of the one before:
 //
 //   1. pass value c[p]: the least over paths in D from a seed of the greatest flood key on the
@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "zt_device.hpp"
+#include "zt_gpu.hpp"
 #include "zt_kernels.hpp"
 
 namespace zt {
@@ -43,27 +44,6 @@ static_assert(kThreads == 256, "four waves per workgroup");
 
 constexpr uint32_t kWsNone = 0xFFFFFFFFu;  // no chain yet / no parent
 constexpr uint32_t kWsOut = 0xFFFFFFFEu;   // outside D
-
-template <int ESZ> struct UIntOf;
-template <> struct UIntOf<1> { using type = uint8_t; };
-template <> struct UIntOf<2> { using type = uint16_t; };
-template <> struct UIntOf<4> { using type = uint32_t; };
-template <> struct UIntOf<8> { using type = uint64_t; };
-
-// storage bits <-> flood key: the rank filters' order key xor `comp` (all ones when descending)
-template <typename K>
-__device__ __forceinline__ K ws_to_key(K b, int mode, K comp) {
-    constexpr K S = (K)((K)1 << (8 * sizeof(K) - 1));
-    const K f = (b & S) ? (K)~(K)0 : S;
-    return (K)(b ^ (mode == kRankKeyFloat ? f : (mode == kRankKeySigned ? S : (K)0)) ^ comp);
-}
-template <typename K>
-__device__ __forceinline__ K ws_from_key(K k, int mode, K comp) {
-    constexpr K S = (K)((K)1 << (8 * sizeof(K) - 1));
-    k = (K)(k ^ comp);
-    const K f = (k & S) ? S : (K)~(K)0;
-    return (K)(k ^ (mode == kRankKeyFloat ? f : (mode == kRankKeySigned ? S : (K)0)));
-}
 
 // a seed element of `ssz` bytes at index i is a label when any bit is set
 __device__ __forceinline__ bool ws_seeded(const uint8_t* seeds, int ssz, int64_t i) {
@@ -104,7 +84,7 @@ __global__ __launch_bounds__(kFlatThreads) void ws_init_kernel(const WsInit g) {
     K* j0 = reinterpret_cast<K*>(g.j0);
     K* domain = reinterpret_cast<K*>(g.domain);
     const K comp = g.descending ? (K)~(K)0 : (K)0;
-    const K top = ws_from_key<K>((K)~(K)0, g.key_mode, comp);  // the greatest flood key, as bits
+    const K top = from_order_key<K>((K)~(K)0, g.key_mode, comp);  // the greatest flood key, as bits
     const K m = (K)g.fgmask;
     const int64_t nvec = (g.n + V - 1) / V;
     for (int64_t v = (int64_t)blockIdx.x * kFlatThreads + threadIdx.x; v < nvec;
@@ -175,7 +155,6 @@ __device__ __forceinline__ uint32_t ws_allowed(int conn) {
 __device__ __forceinline__ uint32_t ws_unless(uint32_t set, int b) {
     return ((set >> b) & 1u) - 1u;
 }
-__device__ __forceinline__ uint32_t umin(uint32_t a, uint32_t b) { return a < b ? a : b; }
 // one more than a distance; "none" stays "none"
 __device__ __forceinline__ uint32_t ws_next(uint32_t d) { return d == kWsNone ? kWsNone : d + 1; }
 
@@ -201,7 +180,7 @@ __global__ __launch_bounds__(kThreads) void ws_dist_kernel(const WsDist g) {
         uint32_t d = kWsOut;
         if (z >= 0 && z < g.Z && y >= 0 && y < g.Y && x >= 0 && x < g.X) {
             const int64_t q = (z * g.Y + y) * g.X + x;
-            k = ws_to_key<K>(c[q], g.key_mode, comp);
+            k = to_order_key<K>(c[q], g.key_mode, comp);
             d = g.src[q];
         }
         sc[i] = k;
@@ -296,20 +275,20 @@ __global__ __launch_bounds__(kThreads) void ws_dist_kernel(const WsDist g) {
 #pragma unroll
                     for (int dz = -1; dz <= 1; ++dz) {
                         if (off + (dz != 0) == 0) continue;
-                        mn[z] = umin(mn[z], col[z + 1 + dz] | ws_unless(eq[z], ws_bit(dz, dy, dx)));
+                        mn[z] = kmin(mn[z], col[z + 1 + dz] | ws_unless(eq[z], ws_bit(dz, dy, dx)));
                     }
                 }
             }
         }
 #pragma unroll
-        for (int z = 0; z < TZ; ++z) nv[z] = umin(cur[z], ws_next(mn[z]));
+        for (int z = 0; z < TZ; ++z) nv[z] = kmin(cur[z], ws_next(mn[z]));
         // along z inside the column: up, then down (each value stays a chain's length)
 #pragma unroll
         for (int z = 1; z < TZ; ++z)
-            nv[z] = umin(nv[z], ws_next(nv[z - 1] | ws_unless(eq[z], ws_bit(-1, 0, 0))));
+            nv[z] = kmin(nv[z], ws_next(nv[z - 1] | ws_unless(eq[z], ws_bit(-1, 0, 0))));
 #pragma unroll
         for (int z = TZ - 2; z >= 0; --z)
-            nv[z] = umin(nv[z], ws_next(nv[z + 1] | ws_unless(eq[z], ws_bit(1, 0, 0))));
+            nv[z] = kmin(nv[z], ws_next(nv[z + 1] | ws_unless(eq[z], ws_bit(1, 0, 0))));
         changed = false;
 #pragma unroll
         for (int z = 0; z < TZ; ++z) changed = changed || nv[z] != cur[z];
@@ -360,7 +339,7 @@ __global__ __launch_bounds__(kFlatThreads) void ws_parent_kernel(const WsParent 
                 parent = (uint32_t)i;
             } else {
                 const int64_t x = i % g.X, r = i / g.X, y = r % g.Y, z = r / g.Y;
-                const K cp = ws_to_key<K>(c[i], g.key_mode, comp);
+                const K cp = to_order_key<K>(c[i], g.key_mode, comp);
                 K best = cp;
 #pragma unroll
                 for (int dz = -1; dz <= 1; ++dz)
@@ -376,7 +355,7 @@ __global__ __launch_bounds__(kFlatThreads) void ws_parent_kernel(const WsParent 
                             const int64_t q = (qz * g.Y + qy) * g.X + qx;
                             const uint32_t dq = g.d[q];
                             if (dq == kWsOut) continue;
-                            const K cq = ws_to_key<K>(c[q], g.key_mode, comp);
+                            const K cq = to_order_key<K>(c[q], g.key_mode, comp);
                             if (d == 0) {
                                 if (cq < best) {
                                     best = cq;
